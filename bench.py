@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- CT slices/s of one fwd+bwd+SGD step of the H-DenseUNet hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config 2d|3dpart|end2end|shard3d] [--dtype bf16|f32]
+    python bench.py --gpus N --steps K --warmup W [--config 2d|3dpart|end2end|shard3d] [--dtype bf16|f32] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 BASELINE.json's metric is "CT slices/sec fwd+bwd (2D 512^2 & 3D 224x224x12)".  The JSON line's top-level `value` is the
@@ -575,22 +575,63 @@ def top_kernels(agg, dtype, k=3):
     return out
 
 
-def run_workload(config, dtype, b, size, cols, steps, warmup, rank, world, use_graph, roofline):
+DUMP_MAX_ELEMS = {"weights": 4 << 20, "states": 4 << 20}   # float32 elements: <= 32 MB in all
+
+
+def _dump_sample(t, name):
+    """the whole flattened tensor when it fits its budget, else a fixed seeded sample of it (the same indices for the same
+    size, in ascending order), as a float32 numpy array"""
+    t = t.detach().float()
+    cap = DUMP_MAX_ELEMS[name]
+    if t.numel() <= cap:
+        return t.cpu().numpy()
+    idx = np.sort(np.random.default_rng(20240611).choice(t.numel(), cap, replace=False))
+    return t.reshape(-1)[torch.as_tensor(idx, device=t.device)].cpu().numpy()
+
+
+def _step_state(m):
+    """the device tensors one training step carries into the next: parameters (moving BN statistics included), SGD velocity,
+    dropout step counter, and the batch moments whose means shift the next step's epilogue statistics"""
+    ctx = m.ctx
+    ts = [ctx.P, ctx.V, ctx.seed_dev]
+    for r in ctx.stat_roots:
+        ts += [r.mean, r.var, r.shift]
+    return ts
+
+
+def dump_outputs(m, loss, out_dir):
+    """--dump-outputs: what a caller of the last timed step receives, as DIR/<name>.npy -- loss (float64 scalar, what
+    train_on_batch returns), weights (the trainable parameters after the step's SGD update) and states (the non-trainable
+    parameters after the step: moving BN statistics, frozen weights); the larger arrays are seeded samples"""
+    os.makedirs(out_dir, exist_ok=True)
+    _sync()
+    ctx = m.ctx
+    arrays = {"loss": np.array(loss, dtype=np.float64),
+              "weights": _dump_sample(ctx.P[:ctx.n_trainable], "weights"),
+              "states": _dump_sample(ctx.P[ctx.n_trainable:], "states")}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def run_workload(config, dtype, b, size, cols, steps, warmup, rank, world, use_graph, roofline, dump_dir=None):
     """dtype "f32x3": the float32 network with the split-bf16 contraction mode switched on for the duration of the workload;
     "f32x3b": exact float32 forward (the parity mode's logits), split contraction in the backward pass only"""
     if dtype not in ("f32x3", "f32x3b"):
-        return _run_workload(config, dtype, dtype, b, size, cols, steps, warmup, rank, world, use_graph, roofline)
+        return _run_workload(config, dtype, dtype, b, size, cols, steps, warmup, rank, world, use_graph, roofline, dump_dir)
     lib = importlib.import_module("h-denseunet_amd").lib
     prev = lib.set_f32_contraction("bf16x3" if dtype == "f32x3" else "bf16x3_bwd")
     try:
-        return _run_workload(config, dtype, "f32", b, size, cols, steps, warmup, rank, world, use_graph, roofline)
+        return _run_workload(config, dtype, "f32", b, size, cols, steps, warmup, rank, world, use_graph, roofline, dump_dir)
     finally:
         lib.set_f32_contraction(prev)
 
 
-def _run_workload(config, dtype, store, b, size, cols, steps, warmup, rank, world, use_graph, roofline):
+def _run_workload(config, dtype, store, b, size, cols, steps, warmup, rank, world, use_graph, roofline, dump_dir=None):
     """build, make resident, (capture,) warm up, time `steps` steps between barriers, MAX over ranks.  Returns the
-    record of this workload (rank 0 adds the roofline of its dominant conv kernel)."""
+    record of this workload (rank 0 adds the roofline of its dominant conv kernel).  With `dump_dir`, rank 0 writes what
+    the last timed step computed there (dump_outputs) before anything else runs on the model.  The reductions of the step
+    use float atomics, so two runs drift apart over the steps before it; to make the dumped step reproducible, the seeded
+    state the model was built with is restored (outside the timed region) before the last timed step."""
     par = importlib.import_module("h-denseunet_amd.parallel")
     synth = importlib.import_module("h-denseunet_amd.synth")
     gcols = cols
@@ -618,6 +659,7 @@ def _run_workload(config, dtype, store, b, size, cols, steps, warmup, rank, worl
     m._upload_x(x)
     m.loss_layer.set_labels(m._labels_internal(y))
     _sync()
+    snap = [t.clone() for t in _step_state(m)] if dump_dir is not None else None
 
     if use_graph:
         m.capture_graph(warmup=1)
@@ -632,13 +674,23 @@ def _run_workload(config, dtype, store, b, size, cols, steps, warmup, rank, worl
         _sync()
 
     shard_mod = importlib.import_module("h-denseunet_amd.shard")
+
+    def timed(n):
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            m.train_step_resident()
+        barrier()
+        return time.perf_counter() - t0
+
     shard_mod.reset_counts()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        m.train_step_resident()
-    barrier()
-    dt = time.perf_counter() - t0
+    if snap is None:
+        dt = timed(steps)
+    else:
+        dt = timed(steps - 1)
+        for t, s in zip(_step_state(m), snap):
+            t.copy_(s)
+        dt += timed(1)
     coll = shard_mod.counts()
     if dist_on:
         t = torch.tensor([dt], device="cpu" if DRYRUN else "cuda")
@@ -647,6 +699,8 @@ def _run_workload(config, dtype, store, b, size, cols, steps, warmup, rank, worl
     ms = dt / steps * 1e3
     slices_per_step = (b if kind == "2d" else cols) * world   # shard3d: cols is per rank -> the whole volume
     loss = m.loss_value()
+    if dump_dir is not None and rank == 0:
+        dump_outputs(m, loss, dump_dir)
     gflop = step_gflop(config, slices_per_step / world, size)
     rec = {
         "workload": WORKLOAD_TEXT[config] % dict(b=b, size=size, cols=cols or 0, gcols=gcols or 0, world=world),
@@ -762,7 +816,12 @@ def main():
                     help="comma list of extra workloads timed after the main one (config[:dtype]); default for the "
                          "default 2d/bf16 run: 3dpart,end2end,shard3d,2d:f32,2d:f32x3b (shard3d = the 512x512x64 per-GPU shard of "
                          "BASELINE configs[4], single GPU only); 'none' disables")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the main workload, write what its last step computed as DIR/<name>.npy "
+                         "(loss, weights, states; float32 / float64, seeded samples of the large arrays, <= 32 MB)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     pkg = importlib.import_module("h-denseunet_amd")
     if DRYRUN:
@@ -782,7 +841,7 @@ def main():
     cols = (a.cols or (64 * world if a.config == "shard3d" else 12)) if a.config != "2d" else None
 
     main_rec = run_workload(a.config, a.dtype, b, size, cols, a.steps, a.warmup, rank, world, not a.no_graph,
-                            not a.no_roofline)
+                            not a.no_roofline, a.dump_outputs)
     extras = a.extras
     if extras is None:
         default_run = a.config == "2d" and a.dtype == "bf16" and a.batch is None and a.size is None

@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -103,3 +105,32 @@ def test_bench_dryrun_float32_split_contraction_extra(emu_lib):
     rec = json.loads(lines[0])
     ex = rec["config"]["extra_workloads"]
     assert [e["dtype"] for e in ex] == ["f32x3", "f32"] and all(e["value"] > 0 for e in ex)
+
+
+def test_bench_dryrun_dump_outputs(emu_lib, tmp_path):
+    """--dump-outputs DIR: after the timed steps the main workload's last step is written as DIR/<name>.npy (float32 / float64,
+    under 64 MB in all) and --steps is the number of timed steps the line reports.  The dumped step starts from the seeded
+    state the model was built with, so two runs -- here even with different step counts -- compute the same thing"""
+    env = dict(os.environ, HIPEMU_THREADS="4", OMP_NUM_THREADS="2")
+    dumps = []
+    for i, steps in enumerate((3, 4)):
+        d = tmp_path / ("run%d" % i)
+        cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_dryrun.py"), "--steps", str(steps), "--warmup", "1", "--batch", "1",
+               "--size", "32", "--extras", "none", "--no-roofline", "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        assert rec["steps"] == steps and rec["ms_per_step"] > 0
+        names = sorted(p.name for p in d.iterdir())
+        assert names == ["loss.npy", "states.npy", "weights.npy"], names
+        arrs = {n[:-4]: np.load(d / n) for n in names}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum((d / n).stat().st_size for n in names) <= 64 << 20
+        assert arrs["weights"].size > 0 and arrs["states"].size > 0
+        assert all(np.isfinite(a).all() for a in arrs.values())
+        assert abs(float(arrs["loss"]) - rec["config"]["loss"]) < 1e-4 * max(1.0, abs(rec["config"]["loss"]))
+        dumps.append(arrs)
+    for n in dumps[0]:
+        np.testing.assert_allclose(dumps[1][n], dumps[0][n], rtol=1e-5, atol=1e-6, err_msg=n)
