@@ -401,3 +401,32 @@ __host__ __device__ __forceinline__ unsigned hdu_hash32(unsigned long long idx, 
   h ^= h >> 16;
   return h;
 }
+
+// integer atomics of the union-find / reduction passes (postproc.hip).  Device-scope atomics execute at the memory side,
+// so their returned values are coherent across XCDs; the relaxed agent-scope load bypasses L1 and may still return an
+// OLDER value of a word that other workgroups decrease -- the union-find is written to tolerate that (postproc.hip).
+#ifdef HDU_EMU
+__device__ __forceinline__ unsigned hdu_atomic_min_u32(unsigned* p, unsigned v) {
+  unsigned old = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (v < old && !__atomic_compare_exchange_n(p, &old, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+  return old;
+}
+__device__ __forceinline__ unsigned hdu_atomic_max_u32(unsigned* p, unsigned v) {
+  unsigned old = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (v > old && !__atomic_compare_exchange_n(p, &old, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+  return old;
+}
+__device__ __forceinline__ unsigned long long hdu_atomic_max_u64(unsigned long long* p, unsigned long long v) {
+  unsigned long long old = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (v > old && !__atomic_compare_exchange_n(p, &old, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+  return old;
+}
+__device__ __forceinline__ unsigned hdu_load_relaxed_u32(const unsigned* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+#else
+__device__ __forceinline__ unsigned hdu_atomic_min_u32(unsigned* p, unsigned v) { return atomicMin(p, v); }
+__device__ __forceinline__ unsigned hdu_atomic_max_u32(unsigned* p, unsigned v) { return atomicMax(p, v); }
+__device__ __forceinline__ unsigned long long hdu_atomic_max_u64(unsigned long long* p, unsigned long long v) { return atomicMax(p, v); }
+__device__ __forceinline__ unsigned hdu_load_relaxed_u32(const unsigned* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+#endif

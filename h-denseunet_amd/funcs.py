@@ -14,6 +14,18 @@ from . import ops
 
 
 def predict_tumor_inwindow(model, imgs_test, num, mini, maxi, args):
+    score, score_num = sweep_scores(model, imgs_test, num, mini, maxi, args)
+    x, y, z = imgs_test.shape[:3]
+    img_deps, img_rows = args.input_size, args.input_size
+    score = score.cpu().numpy() / (score_num.reshape(z, 1, 1, 1) + np.float32(1e-4))        # lib/funcs.py:36
+    out = np.zeros((x, y, z, num), np.float32)
+    out[:img_deps, :img_rows] = score.transpose(1, 2, 0, 3)
+    return out[:, :, :, num - 2], out[:, :, :, num - 1]
+
+
+def sweep_scores(model, imgs_test, num, mini, maxi, args):
+    """the window sweep of predict_tumor_inwindow, left on the device: (score float32 device tensor [z][deps][rows][num] of
+    summed softmax scores, score_num float32 numpy [z] = windows that covered each plane)"""
     batch = args.b
     img_deps, img_rows, img_cols = args.input_size, args.input_size, args.input_cols
     if batch != 1 or model.kind != "hybrid":
@@ -30,7 +42,7 @@ def predict_tumor_inwindow(model, imgs_test, num, mini, maxi, args):
     if not 1 <= num <= 3:
         raise ValueError("num: 1..3 of the 3 class scores (test.py passes 3)")
     score = torch.zeros((z, img_deps, img_rows, num), dtype=torch.float32, device=dev)
-    score_num = np.zeros((z, 1, 1, 1), np.float32)
+    score_num = np.zeros(z, np.float32)
     plane = img_deps * img_rows
     ctx = model.ctx
     a = model.logits.act
@@ -46,10 +58,7 @@ def predict_tumor_inwindow(model, imgs_test, num, mini, maxi, args):
         # first / last slice of each window dropped (lib/funcs.py:33): planes 1 .. img_cols-2 of the logits onto planes c0+1 ..
         ops.softmax_accumulate(a, plane, (img_cols - 2) * plane, num, score[c0 + 1:c0 + img_cols - 1].reshape(-1))
         score_num[c0 + 1:c0 + img_cols - 1] += 1
-    score = score.cpu().numpy() / (score_num + np.float32(1e-4))        # lib/funcs.py:36
-    out = np.zeros((x, y, z, num), np.float32)
-    out[:img_deps, :img_rows] = score.transpose(1, 2, 0, 3)
-    return out[:, :, :, num - 2], out[:, :, :, num - 1]
+    return score, score_num.reshape(z)
 
 
 def liver_window_from_mask(mask):
@@ -99,3 +108,104 @@ def segment_liver_tumor(score1, score2, mask, thres_liver=0.5, thres_tumor=0.8):
     liver_res = ndimage.binary_fill_holes(liver_res.astype(np.uint8)).astype(int)
     liver_res[segmask == 1] = 2
     return liver_res.astype(np.uint8)
+
+
+# ------------------------------------------------------------------ device-resident post-processing (include/hdu.h: hdu_pp_*)
+# Bit-identical to liver_window_from_mask / segment_liver_tumor above (same uint8 volumes, same exceptions): thresholds,
+# largest 26-connected component, dilation and hole filling run as HIP kernels on masks kept in HBM in the host's raster
+# order (x, y, z); only the bounding box, the component counts and the final uint8 label volume come back.
+_NO_COMPONENT = "no foreground component (the reference raises on max([]) here, test.py:90)"
+
+
+def _check_volume(shape):
+    if len(shape) != 3 or min(shape) <= 0:
+        raise ValueError("a 3-D volume is required")
+    n = int(shape[0]) * int(shape[1]) * int(shape[2])
+    if n >= 0xFFFFFFFF:
+        raise ValueError("volumes of 2^32 - 1 voxels or more are not supported")
+    return n
+
+
+def liver_window_from_mask_device(mask):
+    """liver_window_from_mask on the device: `mask` is a host array of any numeric dtype (2 merged into 1, nonzero is the
+    liver); returns (dilated mask as a flat uint8 device tensor in raster order, mini, maxi)"""
+    m = np.asarray(mask)
+    shape = tuple(int(v) for v in m.shape)
+    n = _check_volume(shape)
+    dev = ops.device()
+    src = torch.from_numpy(np.ascontiguousarray(m != 0).view(np.uint8).reshape(n)).to(dev)
+    out = torch.empty(n, dtype=torch.uint8, device=dev)
+    ops.pp_dilate(src, shape, out)
+    box = torch.tensor([-1, -1, -1, 0, 0, 0], dtype=torch.int32, device=dev)
+    ops.pp_bbox(out, shape, box)
+    b = box.cpu().numpy().view(np.uint32).astype(np.int64)
+    if b[0] == 0xFFFFFFFF:
+        raise ValueError("empty liver mask")
+    return out, b[:3], b[3:]
+
+
+class _PostWorkspace:
+    """the uint32 root / area words and the fill flags shared by every pass of one volume"""
+
+    def __init__(self, shape, dev):
+        self.shape, self.n, self.dev = shape, _check_volume(shape), dev
+        self.root = torch.empty(self.n, dtype=torch.int32, device=dev)
+        self.area = torch.empty(self.n, dtype=torch.int32, device=dev)
+        self.flag = torch.empty(self.n, dtype=torch.uint8, device=dev)
+
+    def mask(self):
+        return torch.empty(self.n, dtype=torch.uint8, device=self.dev)
+
+    def largest26(self, binary, out):
+        """out = largest 26-connected component of binary; returns the device word counting the components"""
+        ops.pp_label(binary, self.shape, 26, False, self.root)
+        self.area.zero_()
+        best = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        ncomp = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        ops.pp_largest(self.root, self.shape, self.area, best, ncomp, out)
+        return ncomp
+
+    def fill(self, binary, out):
+        self.flag.zero_()
+        ops.pp_fill_holes(binary, self.shape, self.root, self.flag, out)
+
+
+def segment_liver_tumor_device(score, count, shape, mask_dev, thres_liver=0.5, thres_tumor=0.8):
+    """segment_liver_tumor on the device, from the sweep's own accumulators (sweep_scores): score float32 device tensor
+    [z][deps][rows][num], count the windows per plane ([z], host or device), shape = (x, y, z) of the CT volume, mask_dev
+    the dilated coarse liver mask of liver_window_from_mask_device.  Returns the uint8 label volume (x, y, z)."""
+    shape = tuple(int(v) for v in shape)
+    ws = _PostWorkspace(shape, score.device)
+    if mask_dev.dtype != torch.uint8 or mask_dev.numel() != ws.n or mask_dev.device != score.device:
+        raise ValueError("mask_dev: the uint8 device mask of liver_window_from_mask_device for this volume")
+    if not torch.is_tensor(count):
+        count = torch.from_numpy(np.asarray(count, np.float32).reshape(-1))
+    count = count.to(device=score.device, dtype=torch.float32).contiguous()
+    liver, tumor = ws.mask(), ws.mask()
+    ops.pp_threshold(score.contiguous(), count, shape, thres_liver, thres_tumor, liver, tumor)
+    a, b = ws.mask(), ws.mask()
+    n_liver = ws.largest26(liver, a)                  # liver_res = largest(result1)
+    liver_res = ws.mask()
+    ws.fill(a, liver_res)                             # liver_res = fill_holes(liver_res)
+    ops.pp_dilate(mask_dev.contiguous(), shape, liver)            # the second dilation of test.py:95
+    n_mask = ws.largest26(liver, a)
+    ws.fill(a, b)                                     # liver_labels
+    ops.pp_merge(ops.PP_AND, tumor, b, a)             # Segmask * liver_labels
+    ws.fill(a, b)                                     # Segmask = fill_holes(...)
+    ops.pp_merge(ops.PP_LABEL, liver_res, b, a)       # liver_res[Segmask == 1] = 2
+    counts = torch.cat([n_liver, n_mask]).cpu().numpy()
+    if counts[0] == 0 or counts[1] == 0:
+        raise ValueError(_NO_COMPONENT)
+    return a.cpu().numpy().reshape(shape)
+
+
+def segment_volume(model, imgs_test, liver_mask, args, thres_liver=0.5, thres_tumor=0.9):
+    """test.py:52-112 in one call: the liver window of the coarse mask, the z-sliding-window sweep of `model` and the
+    post-processing, with the scores, masks and labels resident in HBM; returns the uint8 label volume (x, y, z) that
+    segment_liver_tumor(*predict_tumor_inwindow(...), liver_window_from_mask(liver_mask)[0], ...) computes."""
+    shape = tuple(int(v) for v in np.shape(imgs_test)[:3])
+    if tuple(np.shape(liver_mask)) != shape:
+        raise ValueError("liver_mask must have the shape of the CT volume")
+    mask_dev, mini, maxi = liver_window_from_mask_device(liver_mask)
+    score, score_num = sweep_scores(model, imgs_test, 3, mini, maxi, args)
+    return segment_liver_tumor_device(score, score_num, shape, mask_dev, thres_liver, thres_tumor)

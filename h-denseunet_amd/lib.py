@@ -177,6 +177,13 @@ _SIGS = {
     "hdu_cast_pad": (c_int, [c_int, c_p, c_i64, c_int, c_p, c_i64, c_int, c_p]),
     "hdu_cast_out": (c_int, [c_int, c_p, c_i64, c_i64, c_int, c_p, c_p]),
     "hdu_softmax_accumulate": (c_int, [c_int, c_p, c_i64, c_i64, c_int, c_p, c_p]),
+    "hdu_pp_threshold": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_p, c_p, c_p]),
+    "hdu_pp_dilate": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p]),
+    "hdu_pp_label": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
+    "hdu_pp_largest": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p]),
+    "hdu_pp_fill_holes": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
+    "hdu_pp_bbox": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p]),
+    "hdu_pp_merge": (c_int, [c_int, c_p, c_p, c_i64, c_p, c_p]),
     "hdu_zero_regions": (c_int, [c_p, c_int, c_u32, c_p, c_u32, c_p]),
     "hdu_zero": (c_int, [c_p, ctypes.c_uint64, c_p]),
     "hdu_split3_entry_fill": (c_int, [c_p, c_p, c_i64, c_i64, c_int, c_p, c_p, c_int, c_int, c_p, c_u32, ctypes.POINTER(c_u32)]),
@@ -202,7 +209,7 @@ class HduError(RuntimeError):
     pass
 
 
-ABI_VERSION = 7        # include/hdu.h HDU_ABI_VERSION
+ABI_VERSION = 8        # include/hdu.h HDU_ABI_VERSION
 
 
 def product_library_path():

@@ -680,3 +680,50 @@ def softmax_accumulate(logits, row0, M, num, score):
     assert score.dtype == torch.float32 and score.is_contiguous() and score.numel() == M * num
     check(_l.get().hdu_softmax_accumulate(logits.dtype, lp, logits.ld, M, num, ctypes.c_void_p(score.data_ptr()), stream()),
           "hdu_softmax_accumulate")
+
+
+# ------------------------------------------------------------------ post-processing of the inference (include/hdu.h: hdu_pp_*)
+# Volumes are flat tensors of X*Y*Z elements in raster order [X][Y][Z]: uint8 masks, int32 storage for the uint32 root / area
+# words, one int64 word for `best`.
+def _vp(t):
+    assert t.is_contiguous()
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def pp_threshold(score, count, shape, thres_liver, thres_tumor, liver, tumor):
+    """liver / tumour masks of the averaged sweep scores: score float32 [Z][deps][rows][num], count float32 [Z]"""
+    Z, deps, rows, num = score.shape
+    X, Y, Zs = shape
+    assert score.dtype == torch.float32 and count.dtype == torch.float32 and count.numel() == Z == Zs
+    check(_l.get().hdu_pp_threshold(_vp(score), _vp(count), X, Y, Z, deps, rows, num, float(thres_liver), float(thres_tumor),
+                                    _vp(liver), _vp(tumor), stream()), "hdu_pp_threshold")
+
+
+def pp_dilate(src, shape, out):
+    check(_l.get().hdu_pp_dilate(_vp(src), *shape, _vp(out), stream()), "hdu_pp_dilate")
+
+
+def pp_label(mask, shape, connectivity, background, root):
+    check(_l.get().hdu_pp_label(_vp(mask), *shape, connectivity, 1 if background else 0, _vp(root), stream()), "hdu_pp_label")
+
+
+def pp_largest(root, shape, area, best, ncomp, out):
+    """area / best / ncomp must be zeroed"""
+    check(_l.get().hdu_pp_largest(_vp(root), *shape, _vp(area), _vp(best), _vp(ncomp), _vp(out), stream()), "hdu_pp_largest")
+
+
+def pp_fill_holes(mask, shape, root, flag, out):
+    """root: workspace; flag must be zeroed"""
+    check(_l.get().hdu_pp_fill_holes(_vp(mask), *shape, _vp(root), _vp(flag), _vp(out), stream()), "hdu_pp_fill_holes")
+
+
+def pp_bbox(mask, shape, box):
+    """box: int32 [6] = {-1, -1, -1, 0, 0, 0} on entry (uint32 words)"""
+    check(_l.get().hdu_pp_bbox(_vp(mask), *shape, _vp(box), stream()), "hdu_pp_bbox")
+
+
+PP_AND, PP_LABEL = 0, 1
+
+
+def pp_merge(op, a, b, out):
+    check(_l.get().hdu_pp_merge(op, _vp(a), _vp(b), out.numel(), _vp(out), stream()), "hdu_pp_merge")

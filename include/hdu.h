@@ -44,8 +44,8 @@ const char* hdu_backend(void);
  * entry-point set.  A binding compares hdu_abi_version() and hdu_sizeof_conv_desc() with what it was written against and
  * refuses a stale library (h-denseunet_amd/lib.py does): 1 = round 1, 2 = round 2 (splitk_*, bnb_*), 3 = epi_*,
  * 4 = round 3 (hdu_zero_regions, hdu_comm_*), 5 = round 4 (hdu_profile_*, pointwise convs with a fused BN prologue on the
- * DMA path, hdu_wgrad_plan_shape / min_steps), 6 = round 6 (hdu_bn_bwd_apply_sums, bnb_relu bit 2), 7 = round 6 (hdu_split3_*). */
-#define HDU_ABI_VERSION 7
+ * DMA path, hdu_wgrad_plan_shape / min_steps), 6 = round 6 (hdu_bn_bwd_apply_sums, bnb_relu bit 2), 7 = round 6 (hdu_split3_*), 8 = hdu_pp_* (device post-processing). */
+#define HDU_ABI_VERSION 8
 int hdu_abi_version(void);
 size_t hdu_sizeof_conv_desc(void);
 /* Launch profiler (measurement only; replaces nothing in the reference -- Keras has `verbose`, the reference was profiled with
@@ -569,6 +569,40 @@ typedef struct hdu_split3_entry {
 int hdu_split3_entry_fill(hdu_split3_entry* e, const float* src, int64_t ld_src, int64_t rows, int C, const float* a,
                           const float* b, int relu, int pattern, void* dst, uint32_t block_begin, uint32_t* nblocks);
 int hdu_split3_batched(const hdu_split3_entry* dev_table, int n, uint32_t total_blocks, int chl, void* stream);
+
+/* ------------------------------------------------------------------ post-processing of the inference (test.py:52-112)
+ * Device-resident form of h-denseunet_amd/funcs.py liver_window_from_mask / segment_liver_tumor (thresholds, largest
+ * 26-connected component, dilation, hole filling, tumour restricted to the liver), bit-identical to them.  Every mask / label
+ * volume is uint8 (nonzero = set) or uint32 in the host's raster order [X][Y][Z] C-order (x = deps, z = cols); volumes of
+ * 2^32 - 1 voxels or more are refused (HDU_ERR_ARG).  Workspace is caller-owned; "zeroed" words must be 0 on entry.
+ *
+ * hdu_pp_threshold: score [Z][deps][rows][num] float32 and count [Z] float32 as the sweep accumulates them
+ *   (funcs.predict_tumor_inwindow); s = score / (count[z] + 1e-4f) in float32 (IEEE division), 0 for x >= deps or y >= rows;
+ *   tumor = (double)s[num-1] >= thres_tumor, liver = ((double)s[num-2] >= thres_liver) | tumor (channel num-2 taken as a Python
+ *   index: num = 1 reads channel 0).  Thresholds are compared in double as the host compares float64 with a Python float.
+ * hdu_pp_dilate: out = ndimage.binary_dilation(in, iterations=1): 6-connected cross, border 0 (out must not alias in).
+ * hdu_pp_label: union-find connected components of the set voxels (background = 0) or of the clear ones (background = 1),
+ *   connectivity 6 or 26; root[i] = the minimum raster index of i's component, 0xFFFFFFFF off the labelled set.  A fixed
+ *   launch sequence (z-runs, atomic union, flatten); the result does not depend on the schedule.
+ * hdu_pp_largest: out = (root == root of the largest component), ties to the component whose first voxel comes first in
+ *   raster order; area [X*Y*Z] words, best (one 64-bit word) and ncomp (one word) zeroed; ncomp receives the number of
+ *   components (0: out is all zero and the host raises).
+ * hdu_pp_fill_holes: out = ndimage.binary_fill_holes(mask): clear voxels whose 6-connected clear component touches no face
+ *   become set; root [X*Y*Z] words of workspace, flag [X*Y*Z] bytes zeroed.
+ * hdu_pp_bbox: box[0..2] = min x, y, z and box[3..5] = max x, y, z of the set voxels; box = {~0, ~0, ~0, 0, 0, 0} on entry
+ *   (left so for an empty mask).
+ * hdu_pp_merge: HDU_PP_AND: out = a && b;  HDU_PP_LABEL: out = b ? 2 : (a ? 1 : 0)  (test.py: liver_res[segmask == 1] = 2). */
+#define HDU_PP_AND 0
+#define HDU_PP_LABEL 1
+int hdu_pp_threshold(const float* score, const float* count, int X, int Y, int Z, int deps, int rows, int num,
+                     double thres_liver, double thres_tumor, uint8_t* liver, uint8_t* tumor, void* stream);
+int hdu_pp_dilate(const uint8_t* in, int X, int Y, int Z, uint8_t* out, void* stream);
+int hdu_pp_label(const uint8_t* mask, int X, int Y, int Z, int connectivity, int background, uint32_t* root, void* stream);
+int hdu_pp_largest(const uint32_t* root, int X, int Y, int Z, uint32_t* area, uint64_t* best, uint32_t* ncomp, uint8_t* out,
+                   void* stream);
+int hdu_pp_fill_holes(const uint8_t* mask, int X, int Y, int Z, uint32_t* root, uint8_t* flag, uint8_t* out, void* stream);
+int hdu_pp_bbox(const uint8_t* mask, int X, int Y, int Z, uint32_t* box, void* stream);
+int hdu_pp_merge(int op, const uint8_t* a, const uint8_t* b, int64_t n, uint8_t* out, void* stream);
 
 /* ------------------------------------------------------------------ collectives (RCCL over xGMI)
  * The reference's only multi-GPU mechanism is in-graph tower replication (K.utils2/multi_gpu.py:7-69: the gradient sum is
