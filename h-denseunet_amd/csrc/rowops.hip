@@ -1976,20 +1976,93 @@ __global__ __launch_bounds__(256) void cast_out_kernel(const T* __restrict__ src
 }
 
 // score[m][j] += softmax(logits[m][0..2])[j], j < num: the per-window step of the z-sliding-window inference
-// (lib/funcs.py:31-34: K.softmax + K.eval + `score[...] += result`), one thread per voxel, logits read once
+// (lib/funcs.py:31-34: K.softmax + K.eval + `score[...] += result`), one thread per voxel, logits read once.
+// ONE expression for the eager launch (softmax_accumulate_kernel) and the table-driven one (sweep_accumulate_kernel): the two
+// sweeps are bit-equal by construction.
+template <typename T>
+__device__ __forceinline__ void softmax3_add(const T* __restrict__ r, int num, float* __restrict__ o) {
+  const float z0 = Chunk<T>::load1(r), z1 = Chunk<T>::load1(r + 1), z2 = Chunk<T>::load1(r + 2);
+  const float mx = fmaxf(z0, fmaxf(z1, z2));
+  const float e0 = expf(z0 - mx), e1 = expf(z1 - mx), e2 = expf(z2 - mx);
+  const float inv = 1.0f / (e0 + e1 + e2);
+  o[0] += e0 * inv;
+  if (num > 1) o[1] += e1 * inv;
+  if (num > 2) o[2] += e2 * inv;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void softmax_accumulate_kernel(const T* __restrict__ logits, long long ldl, long long M, int num,
                                                                  float* __restrict__ score) {
-  for (long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long long)gridDim.x * blockDim.x) {
-    const T* r = logits + m * ldl;
-    const float z0 = Chunk<T>::load1(r), z1 = Chunk<T>::load1(r + 1), z2 = Chunk<T>::load1(r + 2);
-    const float mx = fmaxf(z0, fmaxf(z1, z2));
-    const float e0 = expf(z0 - mx), e1 = expf(z1 - mx), e2 = expf(z2 - mx);
-    const float inv = 1.0f / (e0 + e1 + e2);
-    float* o = score + m * num;
-    o[0] += e0 * inv;
-    if (num > 1) o[1] += e1 * inv;
-    if (num > 2) o[2] += e2 * inv;
+  for (long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long long)gridDim.x * blockDim.x)
+    softmax3_add(logits + m * ldl, num, score + m * num);
+}
+
+// ------------------------------------------------------------------ table-driven window step (include/hdu.h: hdu_sweep_*)
+// The window position of a captured sweep lives in device memory: starts[nwin] (window start planes) and one cursor word.
+// Every workgroup of the gather and of the accumulate launch reads the same c0 = starts[*cursor]; only the one-thread advance
+// launch between two windows writes the cursor.  Cursor and start are clamped to the table / the volume, so that a corrupt
+// table cannot address outside the buffers.
+__device__ __forceinline__ int sweep_window_start(const int* __restrict__ starts, int nwin, const int* __restrict__ cursor,
+                                                  int c0_max) {
+  int w = *cursor;
+  w = w < 0 ? 0 : (w >= nwin ? nwin - 1 : w);
+  const int c0 = starts[w];
+  return c0 < 0 ? 0 : (c0 > c0_max ? c0_max : c0);
+}
+
+__device__ __forceinline__ float sweep_pre(float v, int pre, float lo, float hi, float mean) {
+  return pre ? fminf(fmaxf(v, lo), hi) - mean : v;      // preprocessing.py:15-16 (clip) + test.py:55 (mean), float32
+}
+
+// dst[0 .. win_planes * plane) = pre(vol[c0 * plane ..]): a scalar head up to dst's 16-byte boundary, 16-byte stores (and
+// 16-byte loads when the source is aligned alike, four scalar loads otherwise), a scalar tail
+__global__ __launch_bounds__(256) void sweep_gather_kernel(const float* __restrict__ vol, int z, long long plane, int win_planes,
+                                                           const int* __restrict__ starts, int nwin,
+                                                           const int* __restrict__ cursor, int pre, float lo, float hi, float mean,
+                                                           float* __restrict__ dst) {
+  const int c0 = sweep_window_start(starts, nwin, cursor, z - win_planes);
+  const float* __restrict__ src = vol + (long long)c0 * plane;
+  const long long n = (long long)win_planes * plane;
+  long long head = (long long)(((16u - (unsigned)((uintptr_t)dst & 15u)) & 15u) >> 2);
+  if (head > n) head = n;
+  const long long n4 = (n - head) >> 2;
+  const bool src16 = ((uintptr_t)(src + head) & 15u) == 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    const float* s = src + head + 4 * i;
+    f32x4 v;
+    if (src16) v = *(const f32x4*)s;
+    else v = f32x4{s[0], s[1], s[2], s[3]};
+    if (pre) v = f32x4{sweep_pre(v.x, 1, lo, hi, mean), sweep_pre(v.y, 1, lo, hi, mean), sweep_pre(v.z, 1, lo, hi, mean),
+                       sweep_pre(v.w, 1, lo, hi, mean)};
+    *(f32x4*)(dst + head + 4 * i) = v;
+  }
+  if (blockIdx.x == 0) {
+    for (long long i = threadIdx.x; i < head; i += 256) dst[i] = sweep_pre(src[i], pre, lo, hi, mean);
+    for (long long i = head + 4 * n4 + threadIdx.x; i < n; i += 256) dst[i] = sweep_pre(src[i], pre, lo, hi, mean);
+  }
+}
+
+// planes 1 .. win_planes-2 of the window's logits onto planes c0+1 .. of score (lib/funcs.py:33 drops the first / last slice of
+// each window); count[c0+1 ..] += 1
+template <typename T>
+__global__ __launch_bounds__(256) void sweep_accumulate_kernel(const T* __restrict__ logits, long long ldl, long long plane,
+                                                               int win_planes, int z, int num, const int* __restrict__ starts,
+                                                               int nwin, const int* __restrict__ cursor,
+                                                               float* __restrict__ score, float* __restrict__ count) {
+  const int c0 = sweep_window_start(starts, nwin, cursor, z - win_planes);
+  const long long M = (long long)(win_planes - 2) * plane;
+  const T* __restrict__ lg = logits + plane * ldl;
+  float* __restrict__ sc = score + (long long)(c0 + 1) * plane * num;
+  for (long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long long)gridDim.x * blockDim.x)
+    softmax3_add(lg + m * ldl, num, sc + m * num);
+  if (blockIdx.x == 0)
+    for (int p = threadIdx.x; p < win_planes - 2; p += 256) count[c0 + 1 + p] += 1.0f;
+}
+
+__global__ void sweep_advance_kernel(int* cursor, int nwin) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const int w = *cursor + 1;
+    *cursor = w < nwin - 1 ? (w < 0 ? 0 : w) : nwin - 1;
   }
 }
 
@@ -2044,6 +2117,38 @@ extern "C" int hdu_softmax_accumulate(int dtype, const void* logits, int64_t ldl
   if (dtype == HDU_BF16) { HDU_T_LAUNCH(bf16_t, softmax_accumulate_kernel, M, (const bf16_t*)logits, (long long)ldl, (long long)M, num, score); }
   else { HDU_T_LAUNCH(float, softmax_accumulate_kernel, M, (const float*)logits, (long long)ldl, (long long)M, num, score); }
   return hdu_check_launch("softmax_accumulate");
+}
+
+extern "C" int hdu_sweep_gather(const float* vol, int z, int64_t plane, int win_planes, const int32_t* starts, int nwin,
+                                const int32_t* cursor, int preprocess, float lo, float hi, float mean, float* dst, void* stream) {
+  if (!vol || !starts || !cursor || !dst) return hdu_set_error(HDU_ERR_ARG, "sweep_gather: null pointer");
+  if (win_planes < 3 || nwin < 1 || plane < 1 || z < win_planes)
+    return hdu_set_error(HDU_ERR_ARG, "sweep_gather: bad args (win_planes >= 3, nwin >= 1, plane >= 1, z >= win_planes)");
+  if (((uintptr_t)vol & 3) || ((uintptr_t)dst & 3)) return hdu_set_error(HDU_ERR_ARG, "sweep_gather: float32 buffers must be 4-byte aligned");
+  if (preprocess && !(lo <= hi)) return hdu_set_error(HDU_ERR_ARG, "sweep_gather: preprocessing needs lo <= hi");
+  const long long n = (long long)win_planes * plane;
+  HDU_LAUNCH(sweep_gather_kernel, dim3(hdu_grid_1d((n + 3) / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream, vol, z,
+             (long long)plane, win_planes, (const int*)starts, nwin, (const int*)cursor, preprocess ? 1 : 0, lo, hi, mean, dst);
+  return hdu_check_launch("sweep_gather");
+}
+
+extern "C" int hdu_sweep_accumulate(int dtype, const void* logits, int64_t ldl, int64_t plane, int win_planes, int z, int num,
+                                    const int32_t* starts, int nwin, const int32_t* cursor, float* score, float* count,
+                                    void* stream) {
+  if (!logits || !starts || !cursor || !score || !count) return hdu_set_error(HDU_ERR_ARG, "sweep_accumulate: null pointer");
+  if (ldl < 3 || num < 1 || num > 3 || win_planes < 3 || nwin < 1 || plane < 1 || z < win_planes)
+    return hdu_set_error(HDU_ERR_ARG, "sweep_accumulate: bad args (3 classes, num in 1..3, win_planes >= 3, nwin >= 1, z >= win_planes)");
+  if (dtype != HDU_BF16 && dtype != HDU_F32) return hdu_set_error(HDU_ERR_ARG, "sweep_accumulate: bad dtype");
+  const long long M = (long long)(win_planes - 2) * plane;
+  if (dtype == HDU_BF16) { HDU_T_LAUNCH(bf16_t, sweep_accumulate_kernel, M, (const bf16_t*)logits, (long long)ldl, (long long)plane, win_planes, z, num, (const int*)starts, nwin, (const int*)cursor, score, count); }
+  else { HDU_T_LAUNCH(float, sweep_accumulate_kernel, M, (const float*)logits, (long long)ldl, (long long)plane, win_planes, z, num, (const int*)starts, nwin, (const int*)cursor, score, count); }
+  return hdu_check_launch("sweep_accumulate");
+}
+
+extern "C" int hdu_sweep_advance(int32_t* cursor, int nwin, void* stream) {
+  if (!cursor || nwin < 1) return hdu_set_error(HDU_ERR_ARG, "sweep_advance: bad args (nwin >= 1)");
+  HDU_LAUNCH(sweep_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)cursor, nwin);
+  return hdu_check_launch("sweep_advance");
 }
 
 // ------------------------------------------------------------------ per-step re-initialisation (include/hdu.h)

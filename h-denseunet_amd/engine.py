@@ -170,6 +170,7 @@ class Ctx:
         self.convs = []
         self.bns = []
         self._fold_plans = {}
+        self._prefolded_phase = None         # prefold(): the phase whose batched fold the caller has already run
         self.prefolded_pass = -1
         # inference-mode BN folds depend on parameters only: all of them (every BN in a predict pass, the frozen ones in
         # a training pass) run as ONE launch at the head of the forward instead of one launch per layer
@@ -574,12 +575,28 @@ class Ctx:
         """ops.conv_desc for a layer of THIS model: a depth shard computes 1 / world of every layer and decides like the whole layer"""
         return ops.conv_desc(*a, shard_world=self.shard_world(), **k)
 
+    def prefold(self):
+        """the batched BN fold of the current phase NOW, outside a captured launch list: every run_forward of this phase skips
+        its own fold launch until end_prefold().  For callers that replay one forward many times on unchanged weights and
+        statistics (sweep.SweepPlan, Model.predict_resident).  Without a batched fold plan nothing is skipped: each BN folds in
+        the forward as usual."""
+        self._prefolded_phase = None
+        if self.batch_fold and self.finalized:
+            plan = self._fold_plan(self.learning_phase)
+            if plan is not None:
+                plan.run()
+                self._prefolded_phase = self.learning_phase
+
+    def end_prefold(self):
+        self._prefolded_phase = None
+
     def run_forward(self):
         self.pass_id += 1
         if self.batch_fold and self.finalized:
             plan = self._fold_plan(self.learning_phase)
             if plan is not None:
-                plan.run()
+                if self._prefolded_phase != self.learning_phase:
+                    plan.run()
                 self.prefolded_pass = self.pass_id
         if self.learning_phase == 1 and self._zeroed_fwd_pass != self.pass_id and self.stats_acc is not None:
             self._zp_arena.run()            # (a training step cleared everything in its step-head launch: step_zero)

@@ -11,10 +11,13 @@ import numpy as np
 import torch
 
 from . import ops
+from . import sweep
 
 
-def predict_tumor_inwindow(model, imgs_test, num, mini, maxi, args):
-    score, score_num = sweep_scores(model, imgs_test, num, mini, maxi, args)
+def predict_tumor_inwindow(model, imgs_test, num, mini, maxi, args, mode="eager"):
+    score, score_num = sweep_scores(model, imgs_test, num, mini, maxi, args, mode=mode)
+    if torch.is_tensor(score_num):
+        score_num = score_num.cpu().numpy()
     x, y, z = imgs_test.shape[:3]
     img_deps, img_rows = args.input_size, args.input_size
     score = score.cpu().numpy() / (score_num.reshape(z, 1, 1, 1) + np.float32(1e-4))        # lib/funcs.py:36
@@ -23,9 +26,16 @@ def predict_tumor_inwindow(model, imgs_test, num, mini, maxi, args):
     return out[:, :, :, num - 2], out[:, :, :, num - 1]
 
 
-def sweep_scores(model, imgs_test, num, mini, maxi, args):
+def sweep_scores(model, imgs_test, num, mini, maxi, args, mode="eager", preprocess=None):
     """the window sweep of predict_tumor_inwindow, left on the device: (score float32 device tensor [z][deps][rows][num] of
-    summed softmax scores, score_num float32 numpy [z] = windows that covered each plane)"""
+    summed softmax scores, score_num float32 [z] = windows that covered each plane).
+    mode="eager" (default): every window driven from the host, score_num counted on the host (numpy).
+    mode="graph": one captured window step replayed per window (sweep.SweepPlan); score and score_num (a DEVICE tensor) are the
+    plan's own accumulators, valid until the next graph-mode sweep of this model.
+    preprocess=(lo, hi, mean): `imgs_test` is raw; the network sees min(max(v, lo), hi) - mean (preprocessing.py:15-16,
+    test.py:55), applied on the host in eager mode and by the window gather in graph mode."""
+    if mode not in ("eager", "graph"):
+        raise ValueError("mode: 'eager' or 'graph', not %r" % (mode,))
     batch = args.b
     img_deps, img_rows, img_cols = args.input_size, args.input_size, args.input_cols
     if batch != 1 or model.kind != "hybrid":
@@ -34,6 +44,11 @@ def sweep_scores(model, imgs_test, num, mini, maxi, args):
     x, y, z = imgs_test.shape[:3]
     if x < img_deps or y < img_rows or z < img_cols:
         raise ValueError("volume smaller than the network window")
+    if mode == "graph":
+        return sweep.plan_for(model, z, num, preprocess).sweep(imgs_test, mini, maxi)
+    if preprocess is not None:
+        lo, hi, mean = (np.float32(v) for v in preprocess)
+        imgs_test = np.clip(np.asarray(imgs_test[:img_deps, :img_rows, :], np.float32), lo, hi) - mean
     right_cols = int(min(z, maxi[2] + 10) - img_cols)
     left_cols = max(0, min(mini[2] - 5, right_cols))
     dev = model.ctx.dev
@@ -199,13 +214,14 @@ def segment_liver_tumor_device(score, count, shape, mask_dev, thres_liver=0.5, t
     return a.cpu().numpy().reshape(shape)
 
 
-def segment_volume(model, imgs_test, liver_mask, args, thres_liver=0.5, thres_tumor=0.9):
+def segment_volume(model, imgs_test, liver_mask, args, thres_liver=0.5, thres_tumor=0.9, mode="eager", preprocess=None):
     """test.py:52-112 in one call: the liver window of the coarse mask, the z-sliding-window sweep of `model` and the
     post-processing, with the scores, masks and labels resident in HBM; returns the uint8 label volume (x, y, z) that
-    segment_liver_tumor(*predict_tumor_inwindow(...), liver_window_from_mask(liver_mask)[0], ...) computes."""
+    segment_liver_tumor(*predict_tumor_inwindow(...), liver_window_from_mask(liver_mask)[0], ...) computes.
+    `mode` / `preprocess`: see sweep_scores (in graph mode the window counts never leave the device)."""
     shape = tuple(int(v) for v in np.shape(imgs_test)[:3])
     if tuple(np.shape(liver_mask)) != shape:
         raise ValueError("liver_mask must have the shape of the CT volume")
     mask_dev, mini, maxi = liver_window_from_mask_device(liver_mask)
-    score, score_num = sweep_scores(model, imgs_test, 3, mini, maxi, args)
+    score, score_num = sweep_scores(model, imgs_test, 3, mini, maxi, args, mode=mode, preprocess=preprocess)
     return segment_liver_tumor_device(score, score_num, shape, mask_dev, thres_liver, thres_tumor)

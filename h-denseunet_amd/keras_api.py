@@ -136,6 +136,10 @@ class Model:
         self.world_size = 1
         self._graph = None
         self._graph_hparams = None
+        self._predict_graph = None       # capture_predict(): the captured learning_phase=0 forward
+        self._predict_captured = False
+        self._predict_key = None
+        self._predict_warm = False       # one eager phase-0 forward has run on a side stream (capture_predict's warm-up)
         self._eager_steps = 0            # eager training steps run so far (capture_graph needs two before it captures)
         self._allreduce = None
         self._allreduce_async = None
@@ -346,16 +350,74 @@ class Model:
         return float(v.item()) / float(self.loss_layer.count * self.world_size)
 
     def predict(self, x, batch_size=None, verbose=0):
-        """forward with learning_phase=0: moving BN statistics everywhere, dropout off."""
-        ctx = self.ctx
+        """forward with learning_phase=0: moving BN statistics everywhere, dropout off (the captured launch list once
+        capture_predict() has been called: same kernels, same order, same output)."""
         self._upload_x(x)
+        self.predict_resident()
+        return self._download_logits().cpu().numpy()
+
+    def _predict_state(self):
+        """what a captured phase-0 launch list bakes in besides the static buffers"""
+        from . import lib as _l
+        return (_l.f32_contraction(), self.ctx.batch_fold)
+
+    def predict_resident(self):
+        """the learning_phase=0 forward on the input already resident in HBM; the logits stay in `self.logits.act`.  After
+        capture_predict() the launch list is one replayed hipGraph.  The weight preparation and the batched BN fold run on every
+        call, outside the graph: a training step, load_weights or set_weights between two calls needs no invalidation."""
+        ctx = self.ctx
+        if self._predict_captured and self._predict_graph is not None and self._predict_key != self._predict_state():
+            self.capture_predict(warmup=0)            # (all buffers are static: a re-capture needs no warm-up)
         ctx.learning_phase = 0
         try:
             ctx.prep_weights()
-            ctx.run_forward()
+            if not self._predict_captured:
+                ctx.run_forward()
+            else:
+                ctx.prefold()
+                if self._predict_graph is not None:
+                    self._predict_graph.replay()
+                else:                                 # emulator build: the same prepared launch list, run eagerly
+                    ctx.run_forward()
         finally:
+            ctx.end_prefold()
             ctx.learning_phase = 1
-        return self._download_logits().cpu().numpy()
+
+    def capture_predict(self, warmup=1):
+        """capture the learning_phase=0 forward of this model (2D, 3D or hybrid) into ONE linear hipGraph; predict() and
+        predict_resident() replay it from then on.  Same pattern as capture_graph: eager warm-up on a side stream first, so that
+        the lazily built device tables (the fold plan of phase 0, scratch buffers) exist before the capture."""
+        from . import lib as _l
+        ctx = self.ctx
+        if ctx.shard_world() > 1:
+            raise RuntimeError("a depth-sharded forward exchanges halos between ranks: no collective is captured")
+        self._predict_graph = None
+        self._predict_captured = False
+        if _l.is_emulator():
+            self._predict_captured = True             # no graphs without a GPU: predict_resident runs the prepared list eagerly
+            self._predict_key = self._predict_state()
+            return
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(warmup if self._predict_warm else max(1, warmup)):
+                self.predict_resident()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        self._predict_warm = True
+        g = torch.cuda.CUDAGraph()
+        ctx.learning_phase = 0
+        try:
+            ctx.prep_weights()
+            ctx.prefold()
+            with _graph_capture(g):
+                ctx.run_forward()
+        finally:
+            ctx.end_prefold()
+            ctx.learning_phase = 1
+        self._predict_graph = g
+        self._predict_captured = True
+        self._predict_key = self._predict_state()
 
     def forward_train_mode(self, x):
         """logits of the training-phase forward (batch statistics), without touching weights; moving statistics

@@ -177,6 +177,9 @@ _SIGS = {
     "hdu_cast_pad": (c_int, [c_int, c_p, c_i64, c_int, c_p, c_i64, c_int, c_p]),
     "hdu_cast_out": (c_int, [c_int, c_p, c_i64, c_i64, c_int, c_p, c_p]),
     "hdu_softmax_accumulate": (c_int, [c_int, c_p, c_i64, c_i64, c_int, c_p, c_p]),
+    "hdu_sweep_gather": (c_int, [c_p, c_int, c_i64, c_int, c_p, c_int, c_p, c_int, c_f, c_f, c_f, c_p, c_p]),
+    "hdu_sweep_accumulate": (c_int, [c_int, c_p, c_i64, c_i64, c_int, c_int, c_int, c_p, c_int, c_p, c_p, c_p, c_p]),
+    "hdu_sweep_advance": (c_int, [c_p, c_int, c_p]),
     "hdu_pp_threshold": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_p, c_p, c_p]),
     "hdu_pp_dilate": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p]),
     "hdu_pp_label": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
@@ -209,7 +212,7 @@ class HduError(RuntimeError):
     pass
 
 
-ABI_VERSION = 8        # include/hdu.h HDU_ABI_VERSION
+ABI_VERSION = 9        # include/hdu.h HDU_ABI_VERSION
 
 
 def product_library_path():

@@ -727,3 +727,34 @@ PP_AND, PP_LABEL = 0, 1
 
 def pp_merge(op, a, b, out):
     check(_l.get().hdu_pp_merge(op, _vp(a), _vp(b), out.numel(), _vp(out), stream()), "hdu_pp_merge")
+
+
+# ------------------------------------------------------------------ table-driven window step (include/hdu.h: hdu_sweep_*)
+# starts: int32 device table of window start planes, cursor: one int32 device word; every launch reads c0 = starts[*cursor].
+def _i32p(t):
+    assert t.dtype == torch.int32 and t.is_contiguous()
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def sweep_gather(vol, z, plane, win_planes, starts, cursor, dst, preprocess=None):
+    """dst[: win_planes * plane] = vol[c0 * plane :] (float32, depth-major [z][plane]); preprocess = (lo, hi, mean) writes
+    min(max(v, lo), hi) - mean instead of the plain copy"""
+    assert vol.dtype == torch.float32 and vol.is_contiguous() and vol.numel() == z * plane
+    assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.numel() >= win_planes * plane
+    lo, hi, mean = (float(v) for v in preprocess) if preprocess is not None else (0.0, 0.0, 0.0)
+    check(_l.get().hdu_sweep_gather(_vp(vol), z, plane, win_planes, _i32p(starts), starts.numel(), _i32p(cursor),
+                                    0 if preprocess is None else 1, lo, hi, mean, _vp(dst), stream()), "hdu_sweep_gather")
+
+
+def sweep_accumulate(logits, plane, win_planes, z, num, starts, cursor, score, count):
+    """score planes c0+1 .. += softmax of logits planes 1 .. win_planes-2 (ops.softmax_accumulate's expression); count likewise += 1"""
+    assert logits.M >= win_planes * plane
+    assert score.dtype == torch.float32 and score.is_contiguous() and score.numel() == z * plane * max(1, min(num, 3))
+    assert count.dtype == torch.float32 and count.is_contiguous() and count.numel() == z
+    check(_l.get().hdu_sweep_accumulate(logits.dtype, logits.ptr, logits.ld, plane, win_planes, z, num, _i32p(starts),
+                                        starts.numel(), _i32p(cursor), _vp(score), _vp(count), stream()), "hdu_sweep_accumulate")
+
+
+def sweep_advance(cursor, nwin):
+    """*cursor = min(*cursor + 1, nwin - 1)"""
+    check(_l.get().hdu_sweep_advance(_i32p(cursor), nwin, stream()), "hdu_sweep_advance")

@@ -45,7 +45,7 @@ const char* hdu_backend(void);
  * refuses a stale library (h-denseunet_amd/lib.py does): 1 = round 1, 2 = round 2 (splitk_*, bnb_*), 3 = epi_*,
  * 4 = round 3 (hdu_zero_regions, hdu_comm_*), 5 = round 4 (hdu_profile_*, pointwise convs with a fused BN prologue on the
  * DMA path, hdu_wgrad_plan_shape / min_steps), 6 = round 6 (hdu_bn_bwd_apply_sums, bnb_relu bit 2), 7 = round 6 (hdu_split3_*), 8 = hdu_pp_* (device post-processing). */
-#define HDU_ABI_VERSION 8
+#define HDU_ABI_VERSION 9
 int hdu_abi_version(void);
 size_t hdu_sizeof_conv_desc(void);
 /* Launch profiler (measurement only; replaces nothing in the reference -- Keras has `verbose`, the reference was profiled with
@@ -512,6 +512,24 @@ int hdu_cast_out(int dtype, const void* src, int64_t ldsrc, int64_t M, int C, fl
  * score[m][j] += softmax(logits[m][0..2])[j] for j < num (num = 3 in test.py), logits [M][ldl] in the compute dtype (3 classes
  * in the first channels), score float32 [M][num].  One pass over the logits; nothing leaves the device. */
 int hdu_softmax_accumulate(int dtype, const void* logits, int64_t ldl, int64_t M, int num, float* score, void* stream);
+
+/* The same window step with the window position in DEVICE memory, so that one captured launch list serves every window of a
+ * sweep (h-denseunet_amd/sweep.py): starts[nwin] int32 = the window start planes (host loop of lib/funcs.py:23-28, the
+ * clamped last window included), cursor = one int32 word; c0 = starts[*cursor].  The kernels clamp the cursor to the table and
+ * c0 to [0, z - win_planes].
+ * hdu_sweep_gather: dst[0 .. win_planes*plane) = vol[c0*plane ..] (vol: float32 [z][plane], the depth-major resident volume;
+ *   dst: the model's float32 input buffer), 16-byte accesses with a scalar head and tail.  preprocess != 0 writes
+ *   min(max(v, lo), hi) - mean in float32 (preprocessing.py:15-16 + test.py:55: a raw-HU volume stays resident); 0 is a
+ *   bit-exact copy.
+ * hdu_sweep_accumulate: hdu_softmax_accumulate (the very expression) of logits planes 1 .. win_planes-2 ([win_planes*plane][ldl],
+ *   compute dtype) onto score planes c0+1 .. (float32 [z][plane][num]); count[c0+1 .. c0+win_planes-2] += 1 (float32 [z]).
+ * hdu_sweep_advance: *cursor = min(*cursor + 1, nwin - 1), one thread; its launch boundary keeps every workgroup of the two
+ *   kernels above on one stable cursor. */
+int hdu_sweep_gather(const float* vol, int z, int64_t plane, int win_planes, const int32_t* starts, int nwin,
+                     const int32_t* cursor, int preprocess, float lo, float hi, float mean, float* dst, void* stream);
+int hdu_sweep_accumulate(int dtype, const void* logits, int64_t ldl, int64_t plane, int win_planes, int z, int num,
+                         const int32_t* starts, int nwin, const int32_t* cursor, float* score, float* count, void* stream);
+int hdu_sweep_advance(int32_t* cursor, int nwin, void* stream);
 
 /* ------------------------------------------------------------------ per-step re-initialisation
  * The accumulators a training step adds into (epilogue statistics, fused BN-backward slot rows, the flat gradient buffer the
