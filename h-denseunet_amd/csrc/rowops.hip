@@ -162,10 +162,46 @@ struct RedK {
   const float* rstd;
   float* partial;  // [gridDim.x][2][C]; slots > 0: a ZEROED [slots][2][C] table, row (blockIdx.x % slots), float atomics
   int slots;
+  // reduce_rows_kernel<.., PW = true> (hdu_bn_bwd_fused_pw): dz / lddz address ONE 16-byte chunk of dy per row, the gradient of the
+  // thread's channels is formed in registers from the filter of the narrow pointwise consumer (pw_dz_chunk)
+  const void* pw_w;     // [C][CH] in the storage dtype: the filter as the consumer's data-gradient launch reads it
+  int pw_K;             // logical classes, <= 4
 };
 
-template <typename T, int MODE, int COLS>
+// hdu_bn_bwd_fused_pw: dz[m][c] = sum_k dy[m][k] * W[c][k] of a pointwise conv with K <= 4 logical outputs, formed where it is used
+// instead of being stored by a data-gradient launch and read back twice.  The thread keeps W[c0 .. c0 + CH)[0 .. K) in registers
+// (pw_load_filter) and turns the row's one dy chunk into the chunk of dz the stored-dz kernels would have loaded: float32 sum of the
+// K products, rounded to the storage dtype (bf16: exactly what the data-gradient launch stores, up to the order of a 3-term float32
+// sum; float32: no rounding).
+template <typename T, int CH>
+__device__ __forceinline__ void pw_load_filter(const void* w, int c0, int K, bool active, float (&wk)[4][CH]) {
+  const T* __restrict__ wp = (const T*)w;
+#pragma unroll
+  for (int j = 0; j < CH; ++j) {
+    float t[CH];
+    Chunk<T>::unpack(*(const u32x4*)(wp + (long long)(active ? c0 + j : 0) * CH), t);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wk[k][j] = k < K ? t[k] : 0.f;
+  }
+}
+template <typename T, int CH>
+__device__ __forceinline__ u32x4 pw_dz_chunk(const u32x4& dyv, const float (&wk)[4][CH], int K) {
+  float d[CH], g[CH];
+  Chunk<T>::unpack(dyv, d);
+#pragma unroll
+  for (int j = 0; j < CH; ++j) {
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k < K) acc += d[k] * wk[k][j];
+    g[j] = acc;
+  }
+  return Chunk<T>::pack(g);
+}
+
+template <typename T, int MODE, int COLS, bool PW = false>
 __global__ __launch_bounds__(256) void reduce_rows_kernel(RedK p) {
+  static_assert(!PW || MODE == RED_BNBWD, "PW: the BN-backward sums only");
   constexpr int CH = Chunk<T>::CH;
   constexpr int ROWS = 256 / COLS;
   __shared__ float red[2][ROWS][COLS * CH];
@@ -180,7 +216,10 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(RedK p) {
   float s1[CH], s2[CH], k0[CH], k1[CH], k2[CH], k3[CH];
 #pragma unroll
   for (int j = 0; j < CH; ++j) { s1[j] = 0.f; s2[j] = 0.f; k0[j] = 0.f; k1[j] = 0.f; k2[j] = 0.f; k3[j] = 0.f; }
+  float wk[PW ? 4 : 1][CH];
+  const long long gc0 = PW ? 0 : c0;          // PW: every column lane of a row reads the row's one dy chunk
   if (active) {
+    if constexpr (PW) pw_load_filter<T, CH>(p.pw_w, c0, p.pw_K, true, wk);
     if (MODE == RED_STATS) {
       // shifted sums: the shift (row 0 of the tensor) removes the cancellation of E[x^2]-E[x]^2
       Chunk<T>::unpack(*(const u32x4*)(xp + c0), k0);
@@ -203,7 +242,8 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(RedK p) {
         for (int j = 0; j < CH; ++j) { const float d = f[j] - k0[j]; s1[j] += d; s2[j] += d * d; }
       } else if (MODE == RED_BNBWD) {
         float g[CH];
-        Chunk<T>::unpack(gv, g);
+        if constexpr (PW) Chunk<T>::unpack(pw_dz_chunk<T, CH>(gv, wk, p.pw_K), g);
+        else Chunk<T>::unpack(gv, g);
 #pragma unroll
         for (int j = 0; j < CH; ++j) {
           const float s = k0[j] * f[j] + k1[j];
@@ -223,7 +263,7 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(RedK p) {
       for (int u = 0; u < ROW_UNROLL; ++u) xv[u] = *(const u32x4*)(xp + (r + u * ROWS) * p.ldx + c0);
       if (MODE == RED_BNBWD) {
 #pragma unroll
-        for (int u = 0; u < ROW_UNROLL; ++u) gv[u] = *(const u32x4*)(dzp + (r + u * ROWS) * p.lddz + c0);
+        for (int u = 0; u < ROW_UNROLL; ++u) gv[u] = *(const u32x4*)(dzp + (r + u * ROWS) * p.lddz + gc0);
       }
       HDU_SCHED_BARRIER();
 #pragma unroll
@@ -231,7 +271,7 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(RedK p) {
     }
     for (; r < r_end; r += ROWS) {
       u32x4 gv = u32x4{0u, 0u, 0u, 0u};
-      if (MODE == RED_BNBWD) gv = *(const u32x4*)(dzp + r * p.lddz + c0);
+      if (MODE == RED_BNBWD) gv = *(const u32x4*)(dzp + r * p.lddz + gc0);
       body(*(const u32x4*)(xp + r * p.ldx + c0), gv);
     }
   }
@@ -326,6 +366,17 @@ static int run_reduce(RedK k, int cols, unsigned gx, unsigned gy, hipStream_t s)
     case 8: HDU_LAUNCH((reduce_rows_kernel<T, MODE, 8>), dim3(gx, gy), dim3(256), 0, s, k); break;
     case 16: HDU_LAUNCH((reduce_rows_kernel<T, MODE, 16>), dim3(gx, gy), dim3(256), 0, s, k); break;
     default: HDU_LAUNCH((reduce_rows_kernel<T, MODE, 32>), dim3(gx, gy), dim3(256), 0, s, k); break;
+  }
+  return 0;
+}
+
+template <typename T>
+static int run_reduce_pw(RedK k, int cols, unsigned gx, unsigned gy, hipStream_t s) {
+  switch (cols) {
+    case 4: HDU_LAUNCH((reduce_rows_kernel<T, RED_BNBWD, 4, true>), dim3(gx, gy), dim3(256), 0, s, k); break;
+    case 8: HDU_LAUNCH((reduce_rows_kernel<T, RED_BNBWD, 8, true>), dim3(gx, gy), dim3(256), 0, s, k); break;
+    case 16: HDU_LAUNCH((reduce_rows_kernel<T, RED_BNBWD, 16, true>), dim3(gx, gy), dim3(256), 0, s, k); break;
+    default: HDU_LAUNCH((reduce_rows_kernel<T, RED_BNBWD, 32, true>), dim3(gx, gy), dim3(256), 0, s, k); break;
   }
   return 0;
 }
@@ -590,6 +641,34 @@ extern "C" int hdu_bn_bwd_finalize_batched(const hdu_bnbwd_entry* table, const u
   return hdu_check_launch("bn_bwd_finalize_batched");
 }
 
+// bias gradients of MANY convs from the [slots][C] column-sum tables the BN-backward apply launches left (bn_bwd_apply_kernel CSUM):
+// one launch at the end of the backward pass instead of a colsum pass + finalize per layer.  Double accumulation over the slot rows,
+// geometry of reduce_finalize_kernel (8 channels x 32 slot lanes).
+__global__ __launch_bounds__(256) void colsum_fold_batched_kernel(const hdu_colsum_entry* __restrict__ table,
+                                                                  const unsigned* __restrict__ begins, int n) {
+  __shared__ double red[2][4][8];
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (begins[mid] <= blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  const hdu_colsum_entry e = table[lo];
+  const int cl = threadIdx.x & 7, pl = threadIdx.x >> 3;
+  const int c = (int)(blockIdx.x - begins[lo]) * 8 + cl;
+  double a1 = 0.0, a2 = 0.0;
+  if (c < e.C)
+    for (int b = pl; b < e.slots; b += 32) a1 += (double)e.partial[(long long)b * e.C + c];
+  fin_reduce32(a1, a2, red);
+  if (pl == 0 && c < e.C) e.out[c] = (float)a1;
+}
+
+extern "C" int hdu_colsum_fold_batched(const hdu_colsum_entry* table, const uint32_t* begins, int n, uint32_t total_blocks,
+                                       void* stream) {
+  if (!table || !begins || n <= 0 || total_blocks == 0) return hdu_set_error(HDU_ERR_ARG, "colsum_fold_batched: bad args");
+  HDU_LAUNCH(colsum_fold_batched_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table, begins, n);
+  return hdu_check_launch("colsum_fold_batched");
+}
+
 __global__ __launch_bounds__(256) void bn_bwd_coef_kernel(int C, float invM, int batch_stats, const float* s1,
                                                           const float* s2, const float* gamma, const float* beta,
                                                           const float* sgamma, const float* rstd, float* k1,
@@ -686,6 +765,13 @@ struct RowK {
   float invM;
   const float* gamma; const float* beta; const float* sgamma; const float* rstd;
   float* dgamma; float* dbeta; float* dsgamma; float* dsbeta;
+  // bn_bwd_apply_kernel<.., PW = true> (hdu_bn_bwd_fused_pw): as RedK's -- dz / lddz address one dy chunk per row
+  const void* pw_w;
+  int pw_K;
+  // bn_bwd_apply_kernel<.., CSUM = true>: column sums of dx AS STORED into row (blockIdx.x % csum_slots) of a zeroed
+  // [csum_slots][C] table (the bias gradient of the conv that produced x: hdu_colsum_fold_batched folds the tables)
+  float* csum;
+  int csum_slots;
 };
 
 // Column totals of a [slots][2][C] slot table for the thread's own CH channels.  The ROWS row lanes of a column chunk split
@@ -785,8 +871,12 @@ __global__ __launch_bounds__(256) void affine_act_kernel(RowK p) {
 // 2 rows per thread the main loop below never ran and its tail loop took the rows one round trip at a time).  Its own instantiation:
 // the 24-36 registers the rows occupy during the prologue cost the LARGE layers an occupancy step (measured in round 3: 2D +0.3 ms when
 // every launch did it) -- a launch of <= 512 workgroups of this size has no occupancy to lose.
-template <typename T, int COLS, bool SUMS = false, bool PRE = false>
+// PW / CSUM (SUMS launches, never PRE): their own instantiations for the same reason -- PW forms dz in registers from one dy chunk per
+// row and the filter of a narrow pointwise consumer (pw_dz_chunk: no stored dz at all); CSUM also sums what the launch stores, per
+// channel (the bias gradient of the conv whose output gradient this launch writes: the separate colsum pass over dx goes).
+template <typename T, int COLS, bool SUMS = false, bool PRE = false, bool PW = false, bool CSUM = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(RowK p) {
+  static_assert(!(PW || CSUM) || (SUMS && !PRE), "PW / CSUM: forms of the SUMS launch without the rows-first prologue");
   constexpr int CH = Chunk<T>::CH;
   constexpr int ROWS = 256 / COLS;
   const int cc = threadIdx.x % COLS, rl = threadIdx.x / COLS;
@@ -836,7 +926,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(RowK p) {
     float T1[CH], T2[CH], S1[CH], S2[CH];
     slot_loads<CH, COLS>(p.sums, p.slots, p.C, cq, active, rl, T1, T2);
     slot_reduce<CH, COLS>(p.slots, cc, rl, T1, T2, S1, S2);
-    if (!active) return;
+    if constexpr (CSUM) { if (!active) r_end = m; }      // (no rows, but this lane still meets the others at the column-sum barrier)
+    else if (!active) return;
 #pragma unroll
     for (int j = 0; j < CH; ++j) {
       const float kk = sg[j] * g[j] * rs[j];
@@ -845,7 +936,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(RowK p) {
       k3[j] = p.batch_stats ? kk * rs[j] * S2[j] * p.invM : 0.f;
       k4[j] = k3[j] * mu[j] - k2;
     }
-    if (blockIdx.x == 0 && rl == 0) {
+    if (blockIdx.x == 0 && rl == 0 && active) {
 #pragma unroll
       for (int j = 0; j < CH; ++j) {
         const int c = c0 + j;
@@ -863,10 +954,18 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(RowK p) {
       k4[j] = p.k3[c] * p.mean[c] - p.k2[c];
     }
   }
+  float wk[PW ? 4 : 1][CH], cs[CSUM ? CH : 1];
+  if constexpr (PW) pw_load_filter<T, CH>(p.pw_w, c0, p.pw_K, active, wk);
+  if constexpr (CSUM) {
+#pragma unroll
+    for (int j = 0; j < CH; ++j) cs[j] = 0.f;
+  }
+  const long long gc0 = PW ? 0 : c0;            // PW: every column lane of a row reads the row's one dy chunk
   auto body = [&](long long m, const u32x4& xv, const u32x4& gv, const u32x4& ov) {
     float f[CH], g[CH], o[CH];
     Chunk<T>::unpack(xv, f);
-    Chunk<T>::unpack(gv, g);
+    if constexpr (PW) Chunk<T>::unpack(pw_dz_chunk<T, CH>(gv, wk, p.pw_K), g);
+    else Chunk<T>::unpack(gv, g);
 #pragma unroll
     for (int j = 0; j < CH; ++j) {
       const float s = a[j] * f[j] + b[j];
@@ -884,7 +983,14 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(RowK p) {
 #pragma unroll
       for (int j = 0; j < CH; ++j) o[j] += old[j];
     }
-    *(u32x4*)(op + m * p.ldo + c0) = Chunk<T>::pack(o);
+    const u32x4 stored = Chunk<T>::pack(o);
+    *(u32x4*)(op + m * p.ldo + c0) = stored;
+    if constexpr (CSUM) {                       // the values as stored: after packing to the storage dtype and the accumulate add
+      float sv[CH];
+      Chunk<T>::unpack(stored, sv);
+#pragma unroll
+      for (int j = 0; j < CH; ++j) cs[j] += sv[j];
+    }
   };
   if constexpr (PRE) {                        // (the host launches this form only when ROW_UNROLL rows per thread cover the row block)
 #pragma unroll
@@ -897,7 +1003,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(RowK p) {
 #pragma unroll
     for (int u = 0; u < ROW_UNROLL; ++u) xv[u] = *(const u32x4*)(xp + (m + u * ROWS) * p.ldx + c0);
 #pragma unroll
-    for (int u = 0; u < ROW_UNROLL; ++u) gv[u] = *(const u32x4*)(dzp + (m + u * ROWS) * p.lddz + c0);
+    for (int u = 0; u < ROW_UNROLL; ++u) gv[u] = *(const u32x4*)(dzp + (m + u * ROWS) * p.lddz + gc0);
 #pragma unroll
     for (int u = 0; u < ROW_UNROLL; ++u) ov[u] = p.accumulate ? *(const u32x4*)(op + (m + u * ROWS) * p.ldo + c0) : z4;
     HDU_SCHED_BARRIER();
@@ -905,8 +1011,24 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(RowK p) {
     for (int u = 0; u < ROW_UNROLL; ++u) body(m + u * ROWS, xv[u], gv[u], ov[u]);
   }
   for (; m < r_end; m += ROWS)
-    body(m, *(const u32x4*)(xp + m * p.ldx + c0), *(const u32x4*)(dzp + m * p.lddz + c0),
+    body(m, *(const u32x4*)(xp + m * p.ldx + c0), *(const u32x4*)(dzp + m * p.lddz + gc0),
          p.accumulate ? *(const u32x4*)(op + m * p.ldo + c0) : z4);
+  if constexpr (CSUM) {
+    // the ROWS row lanes of a column meet in LDS; one float atomic per channel and workgroup (the pattern of the stats / bsum tables)
+    __shared__ float cred[ROWS][COLS * CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) cred[rl][cc * CH + j] = cs[j];
+    __syncthreads();
+    for (int col = threadIdx.x; col < COLS * CH; col += 256) {
+      const int c = blockIdx.y * COLS * CH + col;
+      if (c < p.C) {
+        float t = 0.f;
+#pragma unroll 4
+        for (int r = 0; r < ROWS; ++r) t += cred[r][col];
+        atomicAdd(p.csum + (long long)(blockIdx.x % (unsigned)p.csum_slots) * p.C + c, t);
+      }
+    }
+  }
 }
 
 // du += -corr3*u + corr4 (hdu_bn_bwd_correct): the deferred part of the BN backward of every consumer of these channels
@@ -1383,9 +1505,15 @@ static int bn_bwd_fused_impl(bool reduce, int dtype, const void* dz, int64_t ldd
                              int batch_stats, const float* gamma, const float* beta, const float* sgamma, float* sums,
                              int slots, float* dgamma, float* dbeta, float* dsgamma, float* dsbeta, void* dx,
                              int64_t lddx, int accumulate, float drop_keep, uint32_t drop_seed,
-                             const uint32_t* drop_seed_dev, void* stream) {
+                             const uint32_t* drop_seed_dev, void* stream, float* csum, int csum_slots,
+                             const void* pw_w = nullptr, int pw_K = 0) {
+  // pw_w: dz / lddz are dy / lddy of hdu_bn_bwd_fused_pw (one 16-byte chunk per row), the gradient is formed in registers
+  const bool pw = pw_w != nullptr;
   if (!dz || !x || !a || !b || !mean || !rstd || !sums || !dx) return hdu_set_error(HDU_ERR_ARG, "bn_bwd_fused: null pointer");
   if (slots <= 0 || slots > 32) return hdu_set_error(HDU_ERR_ARG, "bn_bwd_fused: 1 <= slots <= 32");
+  if (csum && (csum_slots <= 0 || ((uintptr_t)csum & 3))) return hdu_set_error(HDU_ERR_ARG, "bn_bwd_fused: column-sum table needs slots >= 1");
+  if (pw && (pw_K < 1 || pw_K > 4 || (((uintptr_t)pw_w | (uintptr_t)dz) & 15)))
+    return hdu_set_error(HDU_ERR_ARG, "bn_bwd_fused_pw: 1 <= K <= 4, dy and the filter 16-byte aligned");
   if (((uintptr_t)sums | (uintptr_t)a | (uintptr_t)b | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma | (uintptr_t)beta |
        (uintptr_t)sgamma) & 15)
     return hdu_set_error(HDU_ERR_ARG, "bn_bwd_fused: per-channel vectors must be 16-byte aligned");
@@ -1401,6 +1529,7 @@ static int bn_bwd_fused_impl(bool reduce, int dtype, const void* dz, int64_t ldd
   k.sums = sums; k.slots = slots; k.batch_stats = batch_stats; k.invM = 1.0f / (float)M;
   k.gamma = gamma; k.beta = beta; k.sgamma = sgamma; k.rstd = rstd;
   k.dgamma = dgamma; k.dbeta = dbeta; k.dsgamma = dsgamma; k.dsbeta = dsbeta;
+  k.pw_w = pw_w; k.pw_K = pw_K; k.csum = csum; k.csum_slots = csum_slots;
   if (int e = rowk_check(dtype, k, "bn_bwd_fused: C / strides must be multiples of the 16-byte chunk")) return e;
   if (M == 0) return 0;
   // launch 1: column sums of (g, g * xhat) into the slot rows (hdu_bn_bwd_apply_sums: the caller's data-gradient epilogue did it)
@@ -1408,17 +1537,21 @@ static int bn_bwd_fused_impl(bool reduce, int dtype, const void* dz, int64_t ldd
     RedK r{};
     r.x = x; r.ldx = ldx; r.dz = dz; r.lddz = lddz; r.M = M; r.C = C;
     r.a = a; r.b = b; r.mean = mean; r.rstd = rstd; r.relu = relu;
-    r.partial = sums; r.slots = slots;
+    r.partial = sums; r.slots = slots; r.pw_w = pw_w; r.pw_K = pw_K;
     int rcols; unsigned rgx, rgy;
     red_geometry(dtype, M, C, &rcols, &rgx, &rgy, &r.rows_per_block);
-    if (dtype == HDU_BF16) run_reduce<bf16_t, RED_BNBWD>(r, rcols, rgx, rgy, (hipStream_t)stream);
+    if (pw) {
+      if (dtype == HDU_BF16) run_reduce_pw<bf16_t>(r, rcols, rgx, rgy, (hipStream_t)stream);
+      else run_reduce_pw<float>(r, rcols, rgx, rgy, (hipStream_t)stream);
+    } else if (dtype == HDU_BF16) run_reduce<bf16_t, RED_BNBWD>(r, rcols, rgx, rgy, (hipStream_t)stream);
     else run_reduce<float, RED_BNBWD>(r, rcols, rgx, rgy, (hipStream_t)stream);
   }
   // launch 2: coefficients from the sums + dx
   int cols; unsigned gx, gy;
   row_geometry(dtype, M, C, &cols, &gx, &gy, &k.rows_per_block);
   // few rows per thread: the form that requests them before the slot rows (bn_bwd_apply_kernel PRE); HDU_TUNE_DEBUG bit 11: off (A/B)
-  const bool pre = k.rows_per_block <= (long long)ROW_UNROLL * (256 / cols) && !(g_tuning[HDU_TUNE_DEBUG] & 2048);
+ // (the PW / CSUM forms have no rows-first variant: the layers that take them have thousands of rows per workgroup)
+  const bool pre = k.rows_per_block <= (long long)ROW_UNROLL * (256 / cols) && !(g_tuning[HDU_TUNE_DEBUG] & 2048) && !pw && !csum;
 #define HDU_APPLY_SUMS(T, PRE)                                                                                                    \
   switch (cols) {                                                                                                                 \
     case 4: HDU_LAUNCH((bn_bwd_apply_kernel<T, 4, true, PRE>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, k); break;        \
@@ -1426,10 +1559,24 @@ static int bn_bwd_fused_impl(bool reduce, int dtype, const void* dz, int64_t ldd
     case 16: HDU_LAUNCH((bn_bwd_apply_kernel<T, 16, true, PRE>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, k); break;      \
     default: HDU_LAUNCH((bn_bwd_apply_kernel<T, 32, true, PRE>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, k); break;      \
   }
-  if (dtype == HDU_BF16) { if (pre) { HDU_APPLY_SUMS(bf16_t, true) } else { HDU_APPLY_SUMS(bf16_t, false) } }
+#define HDU_APPLY_FORM(T, PW, CSUM)                                                                                                        \
+  switch (cols) {                                                                                                                         \
+    case 4: HDU_LAUNCH((bn_bwd_apply_kernel<T, 4, true, false, PW, CSUM>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, k); break;    \
+    case 8: HDU_LAUNCH((bn_bwd_apply_kernel<T, 8, true, false, PW, CSUM>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, k); break;    \
+    case 16: HDU_LAUNCH((bn_bwd_apply_kernel<T, 16, true, false, PW, CSUM>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, k); break;  \
+    default: HDU_LAUNCH((bn_bwd_apply_kernel<T, 32, true, false, PW, CSUM>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, k); break;  \
+  }
+  if (pw || csum) {
+    if (dtype == HDU_BF16) {
+      if (pw && csum) { HDU_APPLY_FORM(bf16_t, true, true) } else if (pw) { HDU_APPLY_FORM(bf16_t, true, false) } else { HDU_APPLY_FORM(bf16_t, false, true) }
+    } else {
+      if (pw && csum) { HDU_APPLY_FORM(float, true, true) } else if (pw) { HDU_APPLY_FORM(float, true, false) } else { HDU_APPLY_FORM(float, false, true) }
+    }
+  } else if (dtype == HDU_BF16) { if (pre) { HDU_APPLY_SUMS(bf16_t, true) } else { HDU_APPLY_SUMS(bf16_t, false) } }
   else { if (pre) { HDU_APPLY_SUMS(float, true) } else { HDU_APPLY_SUMS(float, false) } }
+#undef HDU_APPLY_FORM
 #undef HDU_APPLY_SUMS
-  return hdu_check_launch("bn_bwd_fused");
+  return hdu_check_launch(pw ? "bn_bwd_fused_pw" : "bn_bwd_fused");
 }
 
 extern "C" int hdu_bn_bwd_fused(int dtype, const void* dz, int64_t lddz, const void* x, int64_t ldx, int64_t M, int C,
@@ -1437,9 +1584,24 @@ extern "C" int hdu_bn_bwd_fused(int dtype, const void* dz, int64_t lddz, const v
                                 int batch_stats, const float* gamma, const float* beta, const float* sgamma, float* sums,
                                 int slots, float* dgamma, float* dbeta, float* dsgamma, float* dsbeta, void* dx,
                                 int64_t lddx, int accumulate, float drop_keep, uint32_t drop_seed,
-                                const uint32_t* drop_seed_dev, void* stream) {
+                                const uint32_t* drop_seed_dev, void* stream, float* colsum, int colsum_slots) {
   return bn_bwd_fused_impl(true, dtype, dz, lddz, x, ldx, M, C, a, b, relu, mean, rstd, batch_stats, gamma, beta, sgamma, sums, slots,
-                           dgamma, dbeta, dsgamma, dsbeta, dx, lddx, accumulate, drop_keep, drop_seed, drop_seed_dev, stream);
+                           dgamma, dbeta, dsgamma, dsbeta, dx, lddx, accumulate, drop_keep, drop_seed, drop_seed_dev, stream, colsum,
+                           colsum_slots);
+}
+
+// hdu_bn_bwd_fused whose dz is dy . W of a narrow pointwise consumer (<= 4 logical outputs, ONE stored 16-byte chunk per row): both
+// launches form the gradient in registers, so the consumer's data-gradient launch and the stored dz (written once, read twice) go.
+extern "C" int hdu_bn_bwd_fused_pw(int dtype, const void* dy, int64_t lddy, const void* w, int K, const void* x, int64_t ldx, int64_t M,
+                                   int C, const float* a, const float* b, int relu, const float* mean, const float* rstd,
+                                   int batch_stats, const float* gamma, const float* beta, const float* sgamma, float* sums,
+                                   int slots, float* dgamma, float* dbeta, float* dsgamma, float* dsbeta, void* dx, int64_t lddx,
+                                   int accumulate, float drop_keep, uint32_t drop_seed, const uint32_t* drop_seed_dev, void* stream,
+                                   float* colsum, int colsum_slots) {
+  if (!w) return hdu_set_error(HDU_ERR_ARG, "bn_bwd_fused_pw: null filter");
+  return bn_bwd_fused_impl(true, dtype, dy, lddy, x, ldx, M, C, a, b, relu, mean, rstd, batch_stats, gamma, beta, sgamma, sums, slots,
+                           dgamma, dbeta, dsgamma, dsbeta, dx, lddx, accumulate, drop_keep, drop_seed, drop_seed_dev, stream, colsum,
+                           colsum_slots, w, K);
 }
 
 // Round 6: the apply half alone -- `sums` was filled by the epilogue of the data-gradient launch that produced dz
@@ -1449,9 +1611,10 @@ extern "C" int hdu_bn_bwd_apply_sums(int dtype, const void* dz, int64_t lddz, co
                                      int batch_stats, const float* gamma, const float* beta, const float* sgamma, float* sums,
                                      int slots, float* dgamma, float* dbeta, float* dsgamma, float* dsbeta, void* dx,
                                      int64_t lddx, int accumulate, float drop_keep, uint32_t drop_seed,
-                                     const uint32_t* drop_seed_dev, void* stream) {
+                                     const uint32_t* drop_seed_dev, void* stream, float* colsum, int colsum_slots) {
   return bn_bwd_fused_impl(false, dtype, dz, lddz, x, ldx, M, C, a, b, relu, mean, rstd, batch_stats, gamma, beta, sgamma, sums, slots,
-                           dgamma, dbeta, dsgamma, dsbeta, dx, lddx, accumulate, drop_keep, drop_seed, drop_seed_dev, stream);
+                           dgamma, dbeta, dsgamma, dsbeta, dx, lddx, accumulate, drop_keep, drop_seed, drop_seed_dev, stream, colsum,
+                           colsum_slots);
 }
 
 extern "C" int hdu_bn_bwd_correct(int dtype, const void* u, int64_t ldu, int64_t M, int C, const float* corr3,

@@ -58,6 +58,9 @@ class Var:
             self.needs_grad = False
             self.drop = None  # (keep, seed) if produced through dropout
             self.corr_off = None   # offset of this tensor's [2][ld] deferred-BN-backward accumulators in Ctx.corr_acc
+            self.n_writes = 0      # writers of this tensor's gradient so far in the current backward pass (grad_mode)
+            self.bias_sink = None  # the ConvLayer (trainable, with a bias) whose whole output this tensor is (ConvLayer.csum)
+            self.csum_pass = -1    # pass in which the first writer's BN-backward apply launch also took the bias column sums
         self.C = act.C
 
     def slab(self, c0, C):
@@ -115,6 +118,7 @@ class Var:
                 # the buffer is known, Ctx.step_zero)
                 self.ctx.zero_partial_grad(r.grad_act.buf)
         r.written = True
+        r.n_writes = r.n_writes + 1 if acc else 1
         return acc
 
     # -- batch statistics of the channels of this var (shared by every consumer BN: SURVEY.md section 7)
@@ -194,6 +198,13 @@ class Ctx:
         self.fuse_bn_bwd = self.fuse_bn_bwd_mode > 0
         self.fuse_bn_bwd_pw = os.environ.get("HDU_FUSE_BN_BWD_PW", "1") == "1"
         self.bnb_sums_epilogue = os.environ.get("HDU_BNB_SUMS_EPILOGUE", "1") == "1"      # round 6: ConvLayer._epilogue_sums
+        # a segmentation head (pointwise conv, <= 4 classes in one stored chunk) behind a BN: the BN backward forms dz = dy . W in
+        # registers (hdu_bn_bwd_fused_pw) -- no data-gradient launch, no stored dz (ConvLayer._head_dz_fused); 0 = the three launches
+        self.head_dz_fused = os.environ.get("HDU_HEAD_DZ_FUSED", "1") == "1"
+        # the bias gradient of a conv whose output gradient is written by ONE BN-backward apply launch is summed by that launch
+        # (column-sum table, folded for all such layers by one launch at the end of the pass: ops.ColsumPlan); 0 = ops.colsum per layer
+        self.bias_sums_in_apply = os.environ.get("HDU_BIAS_SUMS_IN_APPLY", "1") == "1"
+        self._csum_deferred, self._csum_plan = [], None
         self.fuse_bn_bwd_now = False
         self.bnb_sinks = []          # (layer, offset into bnb_acc)
         self.bnb_acc = None
@@ -318,15 +329,25 @@ class Ctx:
                 if bn.mode == "batch" or bn.any_trainable():
                     bsum_off[bn] = n_bsum
                     n_bsum += bn.BSUM_SLOTS * 2 * bn.C
+        # column-sum tables of the bias gradients taken inside BN-backward apply launches (bn_bwd_apply_kernel CSUM)
+        n_csum = 0
+        csum_off = {}
+        if self.bias_sums_in_apply and n_bsum and (self.shard is None or self.shard.world == 1):
+            for cv in self.convs:
+                if cv.trainable and cv.bias is not None and cv.out.root is cv.out and cv.out.root.needs_grad \
+                        and cv.out.C == cv.out.act.ld:
+                    csum_off[cv] = n_csum
+                    n_csum += cv.CSUM_SLOTS * cv.cout_p
         # arena layout: [loss sums | epilogue statistics | fused-BN-backward slot rows | deferred corrections | BN-backward
-        # slot tables], every part a multiple of 4 floats so that the parts stay 16-byte aligned
+        # slot tables | bias column-sum tables], every part a multiple of 4 floats so that the parts stay 16-byte aligned
         up4 = lambda n: (n + 3) // 4 * 4
         o_loss, n_loss = 0, 4 * max(1, len(self.loss_layers))
         o_stats = o_loss + n_loss
         o_bnb = o_stats + up4(n_stats)
         o_corr = o_bnb + up4(n_bnb)
         o_bsum = o_corr + up4(self._corr_total)
-        total = o_bsum + up4(n_bsum)
+        o_csum = o_bsum + up4(n_bsum)
+        total = o_csum + up4(n_csum)
         self.arena = torch.zeros(total, dtype=torch.float32, device=self.dev)
         for i, ll in enumerate(self.loss_layers):
             ll.loss_sum = self.arena[4 * i:4 * i + 1]
@@ -336,6 +357,9 @@ class Ctx:
         self.corr_acc = self.arena[o_corr:o_corr + self._corr_total] if self._corr_total else None
         for bn, o in bsum_off.items():
             bn.bsum = self.arena[o_bsum + o:o_bsum + o + bn.BSUM_SLOTS * 2 * bn.C]
+        for cv, o in csum_off.items():
+            cv.csum = self.arena[o_csum + o:o_csum + o + cv.CSUM_SLOTS * cv.cout_p]
+            cv.out.root.bias_sink = cv
         self._shift_copies = [(r.shift, r.mean) for r in self.stat_roots] if self.stats_sinks else []
         self._zp_arena = ops.ZeroPlan([self.arena], self._shift_copies)
         self._zp_bwd = ops.ZeroPlan([self.arena[o_bnb:total]]) if total > o_bnb else None
@@ -621,6 +645,7 @@ class Ctx:
         order = list(reversed(self.bwd))
         if lo == 0:
             self._bnb_deferred = []
+            self._csum_deferred = []
             self._split_now = self.split_wgrad_active()
             if self._split_now and self._split_plan is None:
                 self._build_split_wgrad_plan()
@@ -638,6 +663,11 @@ class Ctx:
                 if self._bnb_plan is None or self._bnb_plan[0] != keys:       # (the set is fixed by the model: built once)
                     self._bnb_plan = (keys, ops.BnBwdPlan([e for _, e in self._bnb_deferred]))
                 self._bnb_plan[1].run()
+            if hi == len(self.bwd) and self._csum_deferred:      # bias gradients from the column-sum tables of the apply launches
+                keys = tuple(k for k, _ in self._csum_deferred)
+                if self._csum_plan is None or self._csum_plan[0] != keys:     # (the set is fixed by the model: built once)
+                    self._csum_plan = (keys, ops.ColsumPlan([e for _, e in self._csum_deferred]))
+                self._csum_plan[1].run()
             if hi == len(self.bwd) and self.wgrad_plan is not None:
                 self.wgrad_plan.run()
             if hi == len(self.bwd) and self._split_now:
@@ -758,11 +788,14 @@ class BNLayer:
                     and self.bsum is not None and xvar.root.needs_grad and ctx._zeroed_bwd_pass == ctx.pass_id
                     and self._bsum_pass != ctx.pass_id)
 
-    def backward(self, xvar, dz_act, sums_ready=False):
+    def backward(self, xvar, dz_act, sums_ready=False, pw=None):
         """dz: gradient w.r.t. relu(a*x+b) at x's resolution.  Writes x.grad and the parameter gradients.
-        sums_ready: the launch that produced dz already added S1 / S2 to this BN's slot table (takes_epilogue_sums)."""
+        sums_ready: the launch that produced dz already added S1 / S2 to this BN's slot table (takes_epilogue_sums).
+        pw = (filter pointer, classes): dz_act is the one-chunk output gradient of the narrow pointwise consumer and dz = dy . W is
+        formed inside the two launches (ConvLayer._head_dz_fused decided that this pass takes the two-launch form)."""
         ctx = self.ctx
         x = xvar.act
+        assert pw is None or self.takes_epilogue_sums(xvar)
         need_sums = self.batch_now or self.any_trainable()
         tr_bn = self.trainable
         tr_sc = self.sg is not None and self.scale_trainable
@@ -787,12 +820,20 @@ class BNLayer:
             self._bsum_pass = ctx.pass_id
             acc = xvar.grad_mode()
             drop = xvar.root.drop if (ctx.dropout_enabled and ctx.learning_phase == 1) else None
+            # the first (usually only) writer of the whole output gradient of a conv with a bias: the apply launch also sums what
+            # it stores per channel -- that conv's bias gradient unless another writer follows (ConvLayer._bias_grad checks)
+            r, sink, csum = xvar.root, xvar.root.bias_sink, None
+            # (folded at the END of the pass: not when gradient buckets must be final as their backward segment ends, batch_wgrad off)
+            if (sink is not None and ctx.bias_sums_in_apply and ctx.batch_wgrad and not acc and xvar.c0 == 0 and xvar.C == r.act.ld
+                    and not (r.corr_off is not None and ctx.corr_acc is not None and ctx.fuse_bn_bwd_now)):
+                csum = sink.csum
+                r.csum_pass = ctx.pass_id
             ops.bn_bwd_fused(dz_act, x, self.a, self.b, self.relu, self.mean_used, self.rstd, self.batch_now,
                              self.gamma.data, self.beta.data, self.sg.data if self.sg else None, self.bsum, self.BSUM_SLOTS,
                              self.gamma.grad if tr_bn else None, self.beta.grad if tr_bn else None,
                              self.sg.grad if tr_sc else None, self.sb.grad if tr_sc else None, xvar.grad, acc,
                              drop[0] if drop else 1.0, drop[1] if drop else 0, ctx.seed_dev if drop else None,
-                             sums_ready=sums_ready)
+                             sums_ready=sums_ready, colsum=csum, colsum_slots=sink.CSUM_SLOTS if csum is not None else 0, pw=pw)
             return
         elif need_sums:   # reduction + coefficients + parameter gradients: two launches
             assert not sums_ready
@@ -853,6 +894,8 @@ class ConvLayer:
         ctx.layer_kind[name] = "conv"
         self.T = K[0] * K[1] * K[2]
         self.cin_p, self.cout_p = cin_p, cout_p
+        self.filters = filters
+        self.csum = None                  # [CSUM_SLOTS][cout_p] column-sum table of the bias gradient, a slice of Ctx.arena (finalize)
         self.dropout = dropout
         if dropout > 0:
             ctx.drop_layers += 1
@@ -1046,7 +1089,7 @@ class ConvLayer:
         x = self.x.act
         if self.trainable and (getattr(self, "in_plan", False) or (ctx._split_now and getattr(self, "in_split_plan", False))):
             if self.bias is not None:      # (the filter gradient itself: deferred to the end of the pass, Ctx.run_backward)
-                ops.colsum(dy, self.bias.grad, ctx.ws)
+                self._bias_grad(dy)
         elif self.trainable:
             if self.xin is not None:
                 d = ctx.conv_desc(self.xin.act, self.wf_ptr, dy, self.K, self.stride, self.pad, self.conv_up)
@@ -1057,7 +1100,7 @@ class ConvLayer:
                                   self.bn.relu if self.bn is not None else False)
             ops.conv_wgrad(d, self.kernel.grad)
             if self.bias is not None:
-                ops.colsum(dy, self.bias.grad, ctx.ws)
+                self._bias_grad(dy)
         if not self.need_input_grad:
             return
         K, pad = self.K, self.pad
@@ -1065,6 +1108,8 @@ class ConvLayer:
             return self._backward_halo(dy)
         if self.bnb_fused and ctx.fuse_bn_bwd_now:
             return self._backward_fused_bn(dy)
+        if self._head_dz_fused():
+            return self.bn.backward(self.x, dy, pw=(self.wd_ptr, self.filters))
         De, He, We = x.D << self.up[0], x.H << self.up[1], x.W << self.up[2]
         direct = self.bn is None and self.up == (0, 0, 0)
         sums_ready = False
@@ -1105,6 +1150,27 @@ class ConvLayer:
             self.bn.backward(self.x, dz, sums_ready=sums_ready)
         else:
             ops.upsample_bwd(dz, self.x.grad, (0, 0, 0), accumulate=self.x.grad_mode())
+
+    def _bias_grad(self, dy):
+        """bias.grad = column sums of dy.  When dy had exactly one writer in this pass and that writer was a BN-backward apply launch
+        that summed what it stored (BNLayer.backward, Var.csum_pass), the sums are already in this layer's table: folded with every
+        other such layer by ONE launch at the end of the pass (Ctx.run_backward).  Otherwise the reduction pass over dy."""
+        ctx, r = self.ctx, self.out.root
+        if self.csum is not None and r.csum_pass == ctx.pass_id and r.n_writes == 1:
+            ctx._csum_deferred.append((id(self), (self.csum, self.CSUM_SLOTS, self.cout_p, self.bias.grad)))
+        else:
+            ops.colsum(dy, self.bias.grad, ctx.ws)
+
+    def _head_dz_fused(self):
+        """A pointwise head with <= 4 classes (ONE stored chunk per pixel) behind a BN whose backward takes the two-launch form in
+        this pass: dz = dy . W (at most 4 terms per element) is formed in registers by those two launches (hdu_bn_bwd_fused_pw)
+        instead of being written by a data-gradient launch and read back twice.  HDU_HEAD_DZ_FUSED=0: off."""
+        ctx, bn = self.ctx, self.bn
+        return bool(ctx.head_dz_fused and bn is not None and self.K == (1, 1, 1) and self.stride == (1, 1, 1)
+                    and self.pad == (0, 0, 0) and self.up == (0, 0, 0) and self.skip is None and not self.halo
+                    and self.cout_p == ops.CHUNK[ctx.dtype] and self.filters <= 4 and self.wd_ptr is not None
+                    and self.wd_ptr.value % 16 == 0 and self.out.grad.ptr.value % 16 == 0
+                    and not (ctx.shard is not None and ctx.shard.world > 1) and bn.takes_epilogue_sums(self.x))
 
     def _epilogue_sums(self, d):
         """Round 6: the backward sums of this conv's input BN (S1 = sum g, S2 = sum g * uhat) ride in the
@@ -1187,6 +1253,7 @@ def _conv_backward_fused_bn(self, dy):
 
 
 ConvLayer._backward_fused_bn = _conv_backward_fused_bn
+ConvLayer.CSUM_SLOTS = int(os.environ.get("HDU_CSUM_SLOTS", "16"))    # slot rows of a bias column-sum table (workgroup % slots), as the BN backward's
 ConvLayer.BNB_SLOTS = int(os.environ.get("HDU_BNB_SLOTS", "16"))      # slot rows of the fused BN backward in a data-gradient epilogue (<= 32).  Round 6 sweep (profiles/r06_experiment_knob_sweep.txt): 16 beats the 32 of rounds 3-5 by 0.1-0.35 % on all three workloads (half the finalize reads), 8 and 4 lose it again to atomic contention
 
 

@@ -75,6 +75,11 @@ class BnBwdEntry(ctypes.Structure):
                 ("sgamma", c_p), ("dgamma", c_p), ("dbeta", c_p), ("dsgamma", c_p), ("dsbeta", c_p)]
 
 
+class ColsumEntry(ctypes.Structure):
+    """include/hdu.h: hdu_colsum_entry"""
+    _fields_ = [("partial", c_p), ("out", c_p), ("slots", ctypes.c_int32), ("C", ctypes.c_int32)]
+
+
 class BnStatsFold(ctypes.Structure):
     """include/hdu.h: hdu_stats_fold_desc"""
     _fields_ = [("partial", c_p), ("slots", ctypes.c_int32), ("Cseg", ctypes.c_int32), ("seg_c0", ctypes.c_int32),
@@ -140,9 +145,12 @@ _SIGS = {
     "hdu_bn_bwd_apply": (c_int, [c_int, c_p, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_p, c_int, c_p, c_p, c_p, c_p,
                                  c_p, c_i64, c_int, c_f, c_u32, c_p, c_p]),
     "hdu_bn_bwd_fused": (c_int, [c_int, c_p, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_p,
-                                 c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_f, c_u32, c_p, c_p]),
+                                 c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_f, c_u32, c_p, c_p, c_p, c_int]),
     "hdu_bn_bwd_apply_sums": (c_int, [c_int, c_p, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_p,
-                                      c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_f, c_u32, c_p, c_p]),
+                                      c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_f, c_u32, c_p, c_p, c_p, c_int]),
+    "hdu_bn_bwd_fused_pw": (c_int, [c_int, c_p, c_i64, c_p, c_int, c_p, c_i64, c_i64, c_int, c_p, c_p, c_int, c_p, c_p, c_int, c_p,
+                                    c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_f, c_u32, c_p, c_p, c_p, c_int]),
+    "hdu_colsum_fold_batched": (c_int, [c_p, c_p, c_int, c_u32, c_p]),
     "hdu_affine_act": (c_int, [c_int, c_p, c_i64, c_i64, c_int, c_p, c_p, c_int, c_p, c_i64, c_p]),
     "hdu_materialize": (c_int, [c_int, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_int, c_int, c_int, c_int,
                                 c_p, c_i64, c_p, c_i64, c_p]),
@@ -212,7 +220,7 @@ class HduError(RuntimeError):
     pass
 
 
-ABI_VERSION = 9        # include/hdu.h HDU_ABI_VERSION
+ABI_VERSION = 10       # include/hdu.h HDU_ABI_VERSION
 
 
 def product_library_path():

@@ -519,17 +519,52 @@ def bn_bwd_apply(dz, x, a, b, relu, mean, k1, k2, k3, dx, accumulate=False, drop
 
 
 def bn_bwd_fused(dz, x, a, b, relu, mean, rstd, batch_stats, gamma, beta, sgamma, sums, slots, dgamma, dbeta, dsgamma,
-                 dsbeta, dx, accumulate=False, drop_keep=1.0, drop_seed=0, drop_seed_dev=None, sums_ready=False):
+                 dsbeta, dx, accumulate=False, drop_keep=1.0, drop_seed=0, drop_seed_dev=None, sums_ready=False, colsum=None,
+                 colsum_slots=0, pw=None):
     """reduction (float atomics into the zeroed [slots][2][C] table `sums`) + coefficients / parameter gradients / dx: two
     launches (include/hdu.h: hdu_bn_bwd_fused); sums_ready: the data-gradient epilogue that produced dz filled `sums`
-    (hdu_conv_desc.bnb_relu bit 2) -- the apply launch alone (hdu_bn_bwd_apply_sums)"""
+    (hdu_conv_desc.bnb_relu bit 2) -- the apply launch alone (hdu_bn_bwd_apply_sums).
+    colsum: zeroed [colsum_slots][C] table that takes the column sums of dx as stored (ColsumPlan folds it).
+    pw = (w_ptr, K): `dz` is the one-chunk output gradient dy of a pointwise conv with K <= 4 logical outputs and w_ptr its
+    data-gradient filter copy -- dz = dy . W is formed in registers (hdu_bn_bwd_fused_pw), no stored dz"""
+    tail = (fptr(a), fptr(b), 1 if relu else 0,
+            fptr(mean), fptr(rstd), 1 if batch_stats else 0, fptr(gamma), fptr(beta), fptr(sgamma),
+            fptr(sums), slots, fptr(dgamma), fptr(dbeta), fptr(dsgamma), fptr(dsbeta), dx.ptr, dx.ld,
+            1 if accumulate else 0, drop_keep, drop_seed,
+            ctypes.c_void_p(drop_seed_dev.data_ptr()) if drop_seed_dev is not None else None,
+            stream(), fptr(colsum), colsum_slots if colsum is not None else 0)
+    if pw is not None:
+        assert not sums_ready and dz.C == CHUNK[x.dtype] and dz.M == x.M
+        check(_l.get().hdu_bn_bwd_fused_pw(x.dtype, dz.ptr, dz.ld, pw[0], pw[1], x.ptr, x.ld, x.M, x.C, *tail), "hdu_bn_bwd_fused_pw")
+        return
     fn = _l.get().hdu_bn_bwd_apply_sums if sums_ready else _l.get().hdu_bn_bwd_fused
-    check(fn(x.dtype, dz.ptr, dz.ld, x.ptr, x.ld, x.M, x.C, fptr(a), fptr(b), 1 if relu else 0,
-             fptr(mean), fptr(rstd), 1 if batch_stats else 0, fptr(gamma), fptr(beta), fptr(sgamma),
-             fptr(sums), slots, fptr(dgamma), fptr(dbeta), fptr(dsgamma), fptr(dsbeta), dx.ptr, dx.ld,
-             1 if accumulate else 0, drop_keep, drop_seed,
-             ctypes.c_void_p(drop_seed_dev.data_ptr()) if drop_seed_dev is not None else None,
-             stream()), "hdu_bn_bwd_fused")
+    check(fn(x.dtype, dz.ptr, dz.ld, x.ptr, x.ld, x.M, x.C, *tail), "hdu_bn_bwd_fused")
+
+
+class ColsumPlan:
+    """bias gradients of many convs from the column-sum tables their BN-backward apply launches filled, as ONE launch
+    (hdu_colsum_fold_batched); built once, tables on device"""
+
+    def __init__(self, entries):
+        """entries: [(partial [slots * C], slots, C, out [C])]"""
+        import numpy as np
+        self.keep = entries
+        n = len(entries)
+        tab = (_l.ColsumEntry * n)()
+        begins = np.zeros(n, dtype=np.uint32)
+        tot = 0
+        for i, (part, slots, C, out) in enumerate(entries):
+            assert part.numel() == slots * C and out.numel() >= C
+            tab[i] = _l.ColsumEntry(part.data_ptr(), out.data_ptr(), slots, C)
+            begins[i] = tot
+            tot += (C + 7) // 8
+        self.n, self.total = n, tot
+        self.table = torch.from_numpy(np.frombuffer(bytes(tab), dtype=np.uint8).copy()).to(device())
+        self.begins = torch.from_numpy(begins.view(np.int32)).to(device())
+
+    def run(self):
+        check(_l.get().hdu_colsum_fold_batched(ctypes.c_void_p(self.table.data_ptr()), ctypes.c_void_p(self.begins.data_ptr()),
+                                               self.n, self.total, stream()), "hdu_colsum_fold_batched")
 
 
 def bn_bwd_finalize(partial, slots, M, C, batch_stats, gamma, beta, sgamma, mean, rstd, dgamma, dbeta, dsgamma, dsbeta,

@@ -44,8 +44,9 @@ const char* hdu_backend(void);
  * entry-point set.  A binding compares hdu_abi_version() and hdu_sizeof_conv_desc() with what it was written against and
  * refuses a stale library (h-denseunet_amd/lib.py does): 1 = round 1, 2 = round 2 (splitk_*, bnb_*), 3 = epi_*,
  * 4 = round 3 (hdu_zero_regions, hdu_comm_*), 5 = round 4 (hdu_profile_*, pointwise convs with a fused BN prologue on the
- * DMA path, hdu_wgrad_plan_shape / min_steps), 6 = round 6 (hdu_bn_bwd_apply_sums, bnb_relu bit 2), 7 = round 6 (hdu_split3_*), 8 = hdu_pp_* (device post-processing). */
-#define HDU_ABI_VERSION 9
+ * DMA path, hdu_wgrad_plan_shape / min_steps), 6 = round 6 (hdu_bn_bwd_apply_sums, bnb_relu bit 2), 7 = round 6 (hdu_split3_*), 8 = hdu_pp_* (device post-processing),
+ * 10 = hdu_bn_bwd_fused_pw, hdu_colsum_fold_batched, column-sum table arguments of hdu_bn_bwd_fused / hdu_bn_bwd_apply_sums. */
+#define HDU_ABI_VERSION 10
 int hdu_abi_version(void);
 size_t hdu_sizeof_conv_desc(void);
 /* Launch profiler (measurement only; replaces nothing in the reference -- Keras has `verbose`, the reference was profiled with
@@ -205,6 +206,16 @@ typedef struct hdu_bnbwd_entry {
   float* dgamma; float* dbeta; float* dsgamma; float* dsbeta;      /* any may be NULL */
 } hdu_bnbwd_entry;
 int hdu_bn_bwd_finalize_batched(const hdu_bnbwd_entry* table, const uint32_t* begins, int n, uint32_t total_blocks, void* stream);
+
+/* ABI 10: bias gradients of MANY convs as ONE launch at the end of the backward pass.  Entry i: out[c] = sum over the slot rows of
+ * partial[slot][c] (double accumulation), partial being the [slots][C] column-sum table an hdu_bn_bwd_fused / _apply_sums /
+ * _fused_pw launch filled (their `colsum` argument).  `begins` / total_blocks as for hdu_bn_bwd_finalize_batched. */
+typedef struct hdu_colsum_entry {
+  const float* partial;      /* [slots][C] */
+  float* out;                /* [C] */
+  int32_t slots, C;
+} hdu_colsum_entry;
+int hdu_colsum_fold_batched(const hdu_colsum_entry* table, const uint32_t* begins, int n, uint32_t total_blocks, void* stream);
 
 /* du[m][c] += -corr3[c]*u[m][c] + corr4[c]: the deferred, reduction-dependent part of the BN backward of every consumer
  * of these channels, applied ONCE, right before their producer reads the gradient. */
@@ -379,12 +390,27 @@ int hdu_bn_bwd_apply(int dtype, const void* dz, int64_t lddz, const void* x, int
  * ([slots][2][C] float32, 1 <= slots <= 32, ZERO on entry: hdu_zero_regions) with float atomics; launch 2 sums the slot rows
  * for its own channels, derives k1 / k2 / k3 in registers (formulas of hdu_bn_bwd_coef) and writes dx like hdu_bn_bwd_apply;
  * its first row block writes the parameter gradients (any of them may be NULL).  Per-channel vectors 16-byte aligned.
- * A finalize launch costs ~4.8 us of pure latency per BatchNormalization (161 of them in one DenseUNet-161 step). */
+ * A finalize launch costs ~4.8 us of pure latency per BatchNormalization (161 of them in one DenseUNet-161 step).
+ * ABI 10: `colsum` (NULL = off): a ZEROED [colsum_slots][C] float32 table; launch 2 adds the column sums of dx AS STORED (after
+ * packing to the storage dtype and after the accumulate add) to row (workgroup % colsum_slots) with float atomics -- when dx is
+ * the complete output gradient of a conv with a bias, that is its bias gradient (folded by hdu_colsum_fold_batched). */
 int hdu_bn_bwd_fused(int dtype, const void* dz, int64_t lddz, const void* x, int64_t ldx, int64_t M, int C, const float* a,
                      const float* b, int relu, const float* mean, const float* rstd, int batch_stats, const float* gamma,
                      const float* beta, const float* sgamma, float* sums, int slots, float* dgamma, float* dbeta,
                      float* dsgamma, float* dsbeta, void* dx, int64_t lddx, int accumulate, float drop_keep,
-                     uint32_t drop_seed, const uint32_t* drop_seed_dev, void* stream);
+                     uint32_t drop_seed, const uint32_t* drop_seed_dev, void* stream, float* colsum, int colsum_slots);
+
+/* ABI 10: hdu_bn_bwd_fused for a BN whose ONLY consumer is a pointwise conv with K <= 4 logical outputs stored as one 16-byte
+ * chunk per pixel (a segmentation head): dz[m][c] = sum_k dy[m][k] * w[c][k] is formed in registers by both launches instead of
+ * being stored by a data-gradient launch and read back twice.  dy / lddy: the conv's output gradient (8 bf16 / 4 f32 per row);
+ * w: [C][8 bf16 | 4 f32], the filter as that data-gradient launch reads it (the copy hdu_weight_prep writes through w_d, so the
+ * same rounded values).  bf16: the float32 sum of the K products is rounded to bf16 before use, as the stored dz was.
+ * Everything else as hdu_bn_bwd_fused. */
+int hdu_bn_bwd_fused_pw(int dtype, const void* dy, int64_t lddy, const void* w, int K, const void* x, int64_t ldx, int64_t M, int C,
+                        const float* a, const float* b, int relu, const float* mean, const float* rstd, int batch_stats,
+                        const float* gamma, const float* beta, const float* sgamma, float* sums, int slots, float* dgamma,
+                        float* dbeta, float* dsgamma, float* dsbeta, void* dx, int64_t lddx, int accumulate, float drop_keep,
+                        uint32_t drop_seed, const uint32_t* drop_seed_dev, void* stream, float* colsum, int colsum_slots);
 
 /* ABI 6: launch 2 of hdu_bn_bwd_fused alone.  `sums` ([slots][2][C]) already holds S1 / S2: the data-gradient launch that produced
  * dz took them in its epilogue (hdu_conv_desc.bnb_relu bit 2 with bnb_partial = sums, bnb_slots = slots).  Replaces the
@@ -393,7 +419,7 @@ int hdu_bn_bwd_apply_sums(int dtype, const void* dz, int64_t lddz, const void* x
                           const float* b, int relu, const float* mean, const float* rstd, int batch_stats, const float* gamma,
                           const float* beta, const float* sgamma, float* sums, int slots, float* dgamma, float* dbeta,
                           float* dsgamma, float* dsbeta, void* dx, int64_t lddx, int accumulate, float drop_keep,
-                          uint32_t drop_seed, const uint32_t* drop_seed_dev, void* stream);
+                          uint32_t drop_seed, const uint32_t* drop_seed_dev, void* stream, float* colsum, int colsum_slots);
 
 /* materialise z = relu?(a*x+b) (needed where the activation is consumed by pooling / as a skip / HFF operand) */
 int hdu_affine_act(int dtype, const void* x, int64_t ldx, int64_t M, int C, const float* a, const float* b,
