@@ -2222,6 +2222,116 @@ __global__ __launch_bounds__(256) void sweep_accumulate_kernel(const T* __restri
     for (int p = threadIdx.x; p < win_planes - 2; p += 256) count[c0 + 1 + p] += 1.0f;
 }
 
+// ------------------------------------------------------------------ window-batched step (include/hdu.h: hdu_sweep_*_batched)
+// `batch` windows per forward: slot i of step *cursor is table entry *cursor * batch + i, clamped to the table and to the volume
+// like sweep_window_start clamps its one entry.
+__device__ __forceinline__ int sweep_slot_start(const int* __restrict__ starts, int ntable, long long entry, int c0_max) {
+  const int w = entry < 0 ? 0 : (entry >= ntable ? ntable - 1 : (int)entry);
+  const int c0 = starts[w];
+  return c0 < 0 ? 0 : (c0 > c0_max ? c0_max : c0);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void slab25d_batched_kernel(const float* __restrict__ vol, int B, int D, int H, int W,
+                                                              T* __restrict__ out, int Cpad) {
+  const long long HW = (long long)H * W, DHW = (long long)D * HW, total = (long long)B * DHW;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const float* __restrict__ v = vol + (i / DHW) * DHW;      // the clamp below stays inside volume b
+    const long long r = i % DHW;
+    const int k = (int)(r / HW);
+    const long long hw = r % HW;
+    const int km = k > 0 ? k - 1 : 0, kp = k < D - 1 ? k + 1 : D - 1;
+    T* o = out + i * Cpad;
+    Chunk<T>::store1(o, v[km * HW + hw]);
+    Chunk<T>::store1(o + 1, v[k * HW + hw]);
+    Chunk<T>::store1(o + 2, v[kp * HW + hw]);
+    for (int j = 3; j < Cpad; ++j) Chunk<T>::store1(o + j, 0.f);
+  }
+}
+
+// slot blockIdx.y: sweep_gather_kernel's copy with the slot's own head and tail (a slot base is only 4-byte aligned in general)
+__global__ __launch_bounds__(256) void sweep_gather_batched_kernel(const float* __restrict__ vol, int z, long long plane,
+                                                                   int win_planes, const int* __restrict__ starts, int ntable,
+                                                                   const int* __restrict__ cursor, int batch, int pre, float lo,
+                                                                   float hi, float mean, float* __restrict__ dst0) {
+  const int slot = blockIdx.y;
+  const int c0 = sweep_slot_start(starts, ntable, (long long)*cursor * batch + slot, z - win_planes);
+  const float* __restrict__ src = vol + (long long)c0 * plane;
+  const long long n = (long long)win_planes * plane;
+  float* __restrict__ dst = dst0 + slot * n;
+  long long head = (long long)(((16u - (unsigned)((uintptr_t)dst & 15u)) & 15u) >> 2);
+  if (head > n) head = n;
+  const long long n4 = (n - head) >> 2;
+  const bool src16 = ((uintptr_t)(src + head) & 15u) == 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    const float* s = src + head + 4 * i;
+    f32x4 v;
+    if (src16) v = *(const f32x4*)s;
+    else v = f32x4{s[0], s[1], s[2], s[3]};
+    if (pre) v = f32x4{sweep_pre(v.x, 1, lo, hi, mean), sweep_pre(v.y, 1, lo, hi, mean), sweep_pre(v.z, 1, lo, hi, mean),
+                       sweep_pre(v.w, 1, lo, hi, mean)};
+    *(f32x4*)(dst + head + 4 * i) = v;
+  }
+  if (blockIdx.x == 0) {
+    for (long long i = threadIdx.x; i < head; i += 256) dst[i] = sweep_pre(src[i], pre, lo, hi, mean);
+    for (long long i = head + 4 * n4 + threadIdx.x; i < n; i += 256) dst[i] = sweep_pre(src[i], pre, lo, hi, mean);
+  }
+}
+
+// The windows of one step overlap (stride win_planes / 4), so this one is written from the score's side: one thread per score
+// voxel of the planes between the first and the last plane any valid slot covers; the voxel's scores are read once, every
+// valid covering slot adds its softmax in slot order (softmax3_add: the eager sweep's sequence of `+=`), and they are stored
+// once.  A plane in that range that no valid slot covers is not written.  No atomics.
+template <typename T>
+__global__ __launch_bounds__(256) void sweep_accumulate_batched_kernel(const T* __restrict__ logits, long long ldl, long long plane,
+                                                                       int win_planes, int z, int num,
+                                                                       const int* __restrict__ starts, int ntable,
+                                                                       const int* __restrict__ nwin_dev,
+                                                                       const int* __restrict__ cursor, int batch,
+                                                                       float* __restrict__ score, float* __restrict__ count) {
+  const long long first = (long long)*cursor * batch;
+  int nwin = *nwin_dev;
+  nwin = nwin < ntable ? nwin : ntable;
+  int c0[HDU_SWEEP_MAX_BATCH];
+  int zlo = z, zhi = -1;                                 // planes zlo .. zhi: what the valid slots cover between them
+#pragma unroll
+  for (int i = 0; i < HDU_SWEEP_MAX_BATCH; ++i) {
+    c0[i] = -1;                                          // (not a valid slot)
+    if (i < batch && first + i < nwin) {
+      c0[i] = sweep_slot_start(starts, ntable, first + i, z - win_planes);
+      zlo = c0[i] + 1 < zlo ? c0[i] + 1 : zlo;
+      zhi = c0[i] + win_planes - 2 > zhi ? c0[i] + win_planes - 2 : zhi;
+    }
+  }
+  if (zhi < zlo) return;
+  const long long M = (long long)(zhi - zlo + 1) * plane;
+  for (long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long long)gridDim.x * blockDim.x) {
+    const int zz = zlo + (int)(m / plane);
+    const long long p = m % plane;
+    float* __restrict__ sc = score + ((long long)zz * plane + p) * num;
+    float o[3] = {sc[0], num > 1 ? sc[1] : 0.f, num > 2 ? sc[2] : 0.f};
+    bool covered = false;
+#pragma unroll
+    for (int i = 0; i < HDU_SWEEP_MAX_BATCH; ++i)
+      if (c0[i] >= 0 && zz >= c0[i] + 1 && zz <= c0[i] + win_planes - 2) {
+        softmax3_add(logits + (((long long)i * win_planes + (zz - c0[i])) * plane + p) * ldl, num, o);
+        covered = true;
+      }
+    if (covered) {
+      sc[0] = o[0];
+      if (num > 1) sc[1] = o[1];
+      if (num > 2) sc[2] = o[2];
+    }
+  }
+  if (blockIdx.x == 0)
+    for (int q = zlo + threadIdx.x; q <= zhi; q += 256) {
+      int cov = 0;
+#pragma unroll
+      for (int i = 0; i < HDU_SWEEP_MAX_BATCH; ++i) cov += (c0[i] >= 0 && q >= c0[i] + 1 && q <= c0[i] + win_planes - 2) ? 1 : 0;
+      for (int i = 0; i < cov; ++i) count[q] += 1.0f;
+    }
+}
+
 __global__ void sweep_advance_kernel(int* cursor, int nwin) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     const int w = *cursor + 1;
@@ -2312,6 +2422,49 @@ extern "C" int hdu_sweep_advance(int32_t* cursor, int nwin, void* stream) {
   if (!cursor || nwin < 1) return hdu_set_error(HDU_ERR_ARG, "sweep_advance: bad args (nwin >= 1)");
   HDU_LAUNCH(sweep_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)cursor, nwin);
   return hdu_check_launch("sweep_advance");
+}
+
+extern "C" int hdu_slab25d_batched(int dtype, const float* vol, int B, int D, int H, int W, void* out, int Cpad, void* stream) {
+  if (!vol || !out || B <= 0 || D <= 0 || H <= 0 || W <= 0 || Cpad < 3) return hdu_set_error(HDU_ERR_ARG, "slab25d_batched: bad args");
+  HDU_CHECK_DTYPE("slab25d_batched");
+  const long long total = (long long)B * D * H * W;
+  if (dtype == HDU_BF16) { HDU_T_LAUNCH(bf16_t, slab25d_batched_kernel, total, vol, B, D, H, W, (bf16_t*)out, Cpad); }
+  else { HDU_T_LAUNCH(float, slab25d_batched_kernel, total, vol, B, D, H, W, (float*)out, Cpad); }
+  return hdu_check_launch("slab25d_batched");
+}
+
+extern "C" int hdu_sweep_gather_batched(const float* vol, int z, int64_t plane, int win_planes, const int32_t* starts, int ntable,
+                                        const int32_t* nwin_dev, const int32_t* cursor, int batch, int preprocess, float lo,
+                                        float hi, float mean, float* dst, void* stream) {
+  if (!vol || !starts || !nwin_dev || !cursor || !dst) return hdu_set_error(HDU_ERR_ARG, "sweep_gather_batched: null pointer");
+  if (win_planes < 3 || ntable < 1 || plane < 1 || z < win_planes || batch < 1 || batch > HDU_SWEEP_MAX_BATCH)
+    return hdu_set_error(HDU_ERR_ARG, "sweep_gather_batched: bad args (win_planes >= 3, ntable >= 1, plane >= 1, z >= win_planes, "
+                                      "batch in 1..8)");
+  if (((uintptr_t)vol & 3) || ((uintptr_t)dst & 3)) return hdu_set_error(HDU_ERR_ARG, "sweep_gather_batched: float32 buffers must be 4-byte aligned");
+  if (preprocess && !(lo <= hi)) return hdu_set_error(HDU_ERR_ARG, "sweep_gather_batched: preprocessing needs lo <= hi");
+  const long long n = (long long)win_planes * plane;
+  HDU_LAUNCH(sweep_gather_batched_kernel, dim3(hdu_grid_1d((n + 3) / 4, 256, 4096), batch), dim3(256), 0, (hipStream_t)stream, vol,
+             z, (long long)plane, win_planes, (const int*)starts, ntable, (const int*)cursor, batch, preprocess ? 1 : 0, lo, hi,
+             mean, dst);
+  return hdu_check_launch("sweep_gather_batched");
+}
+
+extern "C" int hdu_sweep_accumulate_batched(int dtype, const void* logits, int64_t ldl, int64_t plane, int win_planes, int z,
+                                            int num, const int32_t* starts, int ntable, const int32_t* nwin_dev,
+                                            const int32_t* cursor, int batch, float* score, float* count, void* stream) {
+  if (!logits || !starts || !nwin_dev || !cursor || !score || !count)
+    return hdu_set_error(HDU_ERR_ARG, "sweep_accumulate_batched: null pointer");
+  if (ldl < 3 || num < 1 || num > 3 || win_planes < 3 || ntable < 1 || plane < 1 || z < win_planes || batch < 1 ||
+      batch > HDU_SWEEP_MAX_BATCH)
+    return hdu_set_error(HDU_ERR_ARG, "sweep_accumulate_batched: bad args (3 classes, num in 1..3, win_planes >= 3, ntable >= 1, "
+                                      "z >= win_planes, batch in 1..8)");
+  HDU_CHECK_DTYPE("sweep_accumulate_batched");
+  // the planes one step can cover: every slot its win_planes - 2, never more than planes 1 .. z-2 of the volume
+  const long long span = (long long)batch * (win_planes - 2) < z - 2 ? (long long)batch * (win_planes - 2) : z - 2;
+  const long long M = span * plane;
+  if (dtype == HDU_BF16) { HDU_T_LAUNCH(bf16_t, sweep_accumulate_batched_kernel, M, (const bf16_t*)logits, (long long)ldl, (long long)plane, win_planes, z, num, (const int*)starts, ntable, (const int*)nwin_dev, (const int*)cursor, batch, score, count); }
+  else { HDU_T_LAUNCH(float, sweep_accumulate_batched_kernel, M, (const float*)logits, (long long)ldl, (long long)plane, win_planes, z, num, (const int*)starts, ntable, (const int*)nwin_dev, (const int*)cursor, batch, score, count); }
+  return hdu_check_launch("sweep_accumulate_batched");
 }
 
 // ------------------------------------------------------------------ per-step re-initialisation (include/hdu.h)

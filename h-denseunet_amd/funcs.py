@@ -32,6 +32,8 @@ def sweep_scores(model, imgs_test, num, mini, maxi, args, mode="eager", preproce
     mode="eager" (default): every window driven from the host, score_num counted on the host (numpy).
     mode="graph": one captured window step replayed per window (sweep.SweepPlan); score and score_num (a DEVICE tensor) are the
     plan's own accumulators, valid until the next graph-mode sweep of this model.
+    A model built with window_batch = W > 1 runs W windows per forward in either mode (per step, one softmax_accumulate per
+    valid window in window order / one batched accumulate): nothing to pass here.
     preprocess=(lo, hi, mean): `imgs_test` is raw; the network sees min(max(v, lo), hi) - mean (preprocessing.py:15-16,
     test.py:55), applied on the host in eager mode and by the window gather in graph mode."""
     if mode not in ("eager", "graph"):
@@ -61,6 +63,27 @@ def sweep_scores(model, imgs_test, num, mini, maxi, args, mode="eager", preproce
     plane = img_deps * img_rows
     ctx = model.ctx
     a = model.logits.act
+    W = getattr(model, "window_batch", 1)
+    if W > 1:
+        # W windows per forward: padding slots of the last step repeat the last window and add nothing
+        starts = sweep.window_starts(z, img_cols, mini, maxi)
+        n = img_cols * plane
+        for s0 in range(0, len(starts), W):
+            step = starts[s0:s0 + W]
+            for i in range(W):
+                c0 = step[min(i, len(step) - 1)]
+                model.vol[i * n:(i + 1) * n].copy_(vol[c0:c0 + img_cols].reshape(-1))
+            ctx.learning_phase = 0
+            try:
+                ctx.prep_weights()
+                ctx.run_forward()
+            finally:
+                ctx.learning_phase = 1
+            for i, c0 in enumerate(step):
+                ops.softmax_accumulate(a, (i * img_cols + 1) * plane, (img_cols - 2) * plane, num,
+                                       score[c0 + 1:c0 + img_cols - 1].reshape(-1))
+                score_num[c0 + 1:c0 + img_cols - 1] += 1
+        return score, score_num.reshape(z)
     for cols in range(left_cols, right_cols + window_cols, window_cols):
         c0 = z - img_cols if cols > z - img_cols else cols        # lib/funcs.py:26-28: last window is clamped
         model.vol.copy_(vol[c0:c0 + img_cols].reshape(-1))

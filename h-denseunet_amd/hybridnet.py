@@ -5,12 +5,14 @@ import os
 from .keras_api import Model
 
 
-def dense_rnn_net(args, dtype=None, nb_layers2d=(6, 12, 36, 24), nb_layers3d=(3, 4, 12, 8), seed=4321, shard=None):
+def dense_rnn_net(args, dtype=None, nb_layers2d=(6, 12, 36, 24), nb_layers3d=(3, 4, 12, 8), seed=4321, shard=None, window_batch=1):
     """shard (shard.ShardInfo): this process holds args.input_cols depth planes of ONE volume split over the ranks
-    (new capability; the reference has batch towers only)."""
+    (new capability; the reference has batch towers only).
+    window_batch = W in 2..8: an inference-only model that runs W sliding windows per forward (keras_api.Model)."""
     dtype = dtype or os.environ.get("HDU_DTYPE", "bf16")
     return Model("hybrid", args.b, args.input_size, args.input_cols, dtype=dtype, variant="end2end",
-                 name="auto3d_residual_conv", nb_layers2d=tuple(nb_layers2d), nb_layers3d=tuple(nb_layers3d), seed=seed, shard=shard)
+                 name="auto3d_residual_conv", nb_layers2d=tuple(nb_layers2d), nb_layers3d=tuple(nb_layers3d), seed=seed, shard=shard,
+                 window_batch=window_batch)
 
 
 _VARIANT = "end2end"

@@ -67,8 +67,16 @@ class History:
 
 class Model:
     def __init__(self, kind, args_b, input_size, input_cols=None, dtype="bf16", variant=None, name=None,
-                 nb_layers2d=(6, 12, 36, 24), nb_layers3d=(3, 4, 12, 8), seed=4321, shard=None):
+                 nb_layers2d=(6, 12, 36, 24), nb_layers3d=(3, 4, 12, 8), seed=4321, shard=None, window_batch=1):
         self.kind = kind                  # "2d" | "hybrid" | "3d"
+        # window_batch = W > 1 (hybrid only): W independent windows of a sliding-window sweep per forward, depth-major back to
+        # back in `vol`.  Inference only: the reference cannot build a hybrid at b > 1 (hybridnet.py:359-364), so its
+        # batch-statistics BNs and its 1:7 loss slice have no semantics to pin there.  Weights and layer names are those of W = 1.
+        if not isinstance(window_batch, int) or not 1 <= window_batch <= ops.SWEEP_MAX_BATCH:
+            raise ValueError("window_batch: 1..%d windows per forward, not %r" % (ops.SWEEP_MAX_BATCH, window_batch))
+        if window_batch > 1 and (kind != "hybrid" or shard is not None):
+            raise ValueError("window_batch > 1 needs an unsharded hybrid net")
+        self.window_batch = window_batch
         self.name = name
         self.dtype = HDU_BF16 if dtype in ("bf16", HDU_BF16) else HDU_F32
         self.variant = variant
@@ -92,7 +100,7 @@ class Model:
             D = input_cols
             ctx.shard = shard
             sharded = shard is not None and shard.world > 1
-            self.input_shape = (1, H, W, D, 1)
+            self.input_shape = (window_batch, H, W, D, 1)
             if sharded:
                 # input_cols = depth planes held by THIS rank; one raw CT plane of each depth neighbour rides along for
                 # the 2.5D slabs (denseunet3d.py:399-409): vol_h = [halo][D planes][halo], vol = its interior
@@ -101,9 +109,9 @@ class Model:
                 self.logits = _m.build_hybrid(ctx, self.vol_h, D, H, W, variant=variant, nb_layers2d=nb_layers2d,
                                               nb_layers3d=nb_layers3d)
             else:
-                self.vol = torch.zeros(D * H * W, dtype=torch.float32, device=ctx.dev)
+                self.vol = torch.zeros(window_batch * D * H * W, dtype=torch.float32, device=ctx.dev)
                 self.logits = _m.build_hybrid(ctx, self.vol, D, H, W, variant=variant, nb_layers2d=nb_layers2d,
-                                              nb_layers3d=nb_layers3d)
+                                              nb_layers3d=nb_layers3d, batch=window_batch)
             # loss.py:6-7 hard-codes depth slices 1:7 (of the WHOLE volume: a shard takes its part of that range)
             g0 = shard.rank * D if sharded else 0
             world = shard.world if sharded else 1
@@ -112,7 +120,7 @@ class Model:
             self.loss_layer = LossLayer(ctx, self.logits, ranges)
             if sharded:   # normalised by the global voxel count: count * world == (min(7, D_global) - 1) * H * W
                 self.loss_layer.count = (min(7, D * world) - 1) * H * W / float(world)
-            self.output_shape = (1, H, W, D, 3)
+            self.output_shape = (window_batch, H, W, D, 3)
         elif kind == "3d":
             # stand-alone DenseNet3D on a 4-channel volume; with `shard` this rank holds input_cols LOCAL depth planes
             if args_b != 1:
@@ -159,8 +167,8 @@ class Model:
             self.x_stage.copy_(x.reshape(-1).to(self.ctx.dev), non_blocking=True)
         elif self.kind == "3d":  # (1,H,W,D,4) -> depth-major [D][H][W][4]
             self.x_stage.copy_(x[0].permute(2, 0, 1, 3).contiguous().reshape(-1).to(self.ctx.dev))
-        else:  # (1,H,W,D,1) -> depth-major [D][H][W]
-            self.vol.copy_(x[0, :, :, :, 0].permute(2, 0, 1).contiguous().reshape(-1).to(self.ctx.dev))
+        else:  # (W,H,W,D,1) -> W depth-major windows [D][H][W] back to back (W = window_batch, 1 by default)
+            self.vol.copy_(x[:, :, :, :, 0].permute(0, 3, 1, 2).contiguous().reshape(-1).to(self.ctx.dev))
             if getattr(self, "vol_h", None) is not None:
                 from . import shard as _sh
                 H, D = self.input_shape[1], self.input_shape[3]
@@ -184,7 +192,12 @@ class Model:
         o = self.out_stage.reshape(a.N, a.D, a.H, a.W, 3)
         if self.kind == "2d":
             return o[:, 0]
-        return o.permute(0, 2, 3, 1, 4)   # (1,D,H,W,3) -> (1,H,W,D,3)
+        return o.permute(0, 2, 3, 1, 4)   # (N,D,H,W,3) -> (N,H,W,D,3)
+
+    def _inference_only(self, what):
+        if self.window_batch > 1:
+            raise ValueError("%s: a window_batch=%d model is inference-only (predict / capture_predict / the sweeps)"
+                             % (what, self.window_batch))
 
     # ------------------------------------------------------------------ Keras surface
     def compile(self, optimizer, loss=None, **kw):
@@ -241,6 +254,7 @@ class Model:
 
     def train_step_resident(self):
         """one fwd+bwd+SGD step on the inputs / labels already resident in HBM (what bench.py times)."""
+        self._inference_only("train_step_resident")
         if self.optimizer is None:
             raise RuntimeError("compile() the model first")
         if self._graph is not None and self._graph_hparams != (self.optimizer.lr, self.optimizer.momentum):
@@ -289,6 +303,7 @@ class Model:
     def capture_graph(self, warmup=2):
         """capture the step into hipGraphs.  Single GPU: ONE graph (fwd + bwd + SGD).  Data parallel: the gradient
         all-reduce stays an eager RCCL call between two graphs (fwd+bwd | SGD update) -- no collective is captured."""
+        self._inference_only("capture_graph")
         if self.optimizer is None:
             raise RuntimeError("compile() the model first")
         if self.optimizer.decay > 0:
@@ -333,6 +348,7 @@ class Model:
         self._graph_hparams = (self.optimizer.lr, self.optimizer.momentum)
 
     def train_on_batch(self, x, y=None, **kw):
+        self._inference_only("train_on_batch")
         if hasattr(x, "fill_model"):
             # augment.DeviceBatch: the sample assembly kernels write input and labels straight into the model's buffers
             x.fill_model(self)
@@ -422,6 +438,7 @@ class Model:
     def forward_train_mode(self, x):
         """logits of the training-phase forward (batch statistics), without touching weights; moving statistics
         ARE updated exactly as in a training step.  Used by the parity tests."""
+        self._inference_only("forward_train_mode")
         self._upload_x(x)
         self.ctx.learning_phase = 1
         self.ctx.prep_weights()
@@ -433,6 +450,7 @@ class Model:
 
     def fit_generator(self, generator, steps_per_epoch, epochs=1, verbose=1, callbacks=None, max_queue_size=10,
                       workers=1, use_multiprocessing=False, **kw):
+        self._inference_only("fit_generator")
         hist = History()
         callbacks = callbacks or []
         for cb in callbacks:

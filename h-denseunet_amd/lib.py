@@ -180,6 +180,7 @@ _SIGS = {
                              c_sz, c_p]),
     "hdu_sgd_nesterov": (c_int, [c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_p]),
     "hdu_slab25d": (c_int, [c_int, c_p, c_int, c_int, c_int, c_p, c_int, c_p]),
+    "hdu_slab25d_batched": (c_int, [c_int, c_p, c_int, c_int, c_int, c_int, c_p, c_int, c_p]),
     "hdu_make_input3d": (c_int, [c_int, c_p, c_p, c_i64, c_f, c_int, c_int, c_int, c_p, c_int, c_p]),
     "hdu_make_input3d_bwd": (c_int, [c_int, c_p, c_int, c_f, c_i64, c_p, c_i64, c_int, c_int, c_p]),
     "hdu_cast_pad": (c_int, [c_int, c_p, c_i64, c_int, c_p, c_i64, c_int, c_p]),
@@ -188,6 +189,9 @@ _SIGS = {
     "hdu_sweep_gather": (c_int, [c_p, c_int, c_i64, c_int, c_p, c_int, c_p, c_int, c_f, c_f, c_f, c_p, c_p]),
     "hdu_sweep_accumulate": (c_int, [c_int, c_p, c_i64, c_i64, c_int, c_int, c_int, c_p, c_int, c_p, c_p, c_p, c_p]),
     "hdu_sweep_advance": (c_int, [c_p, c_int, c_p]),
+    "hdu_sweep_gather_batched": (c_int, [c_p, c_int, c_i64, c_int, c_p, c_int, c_p, c_p, c_int, c_int, c_f, c_f, c_f, c_p, c_p]),
+    "hdu_sweep_accumulate_batched": (c_int, [c_int, c_p, c_i64, c_i64, c_int, c_int, c_int, c_p, c_int, c_p, c_p, c_int, c_p,
+                                             c_p, c_p]),
     "hdu_pp_threshold": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_p, c_p, c_p]),
     "hdu_pp_dilate": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p]),
     "hdu_pp_label": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
@@ -220,7 +224,7 @@ class HduError(RuntimeError):
     pass
 
 
-ABI_VERSION = 10       # include/hdu.h HDU_ABI_VERSION
+ABI_VERSION = 11       # include/hdu.h HDU_ABI_VERSION
 
 
 def product_library_path():

@@ -228,13 +228,16 @@ def build_dense_net_3d(ctx, x_in, variant="3dpart", reduction=0.5, nb_layers=(3,
 class Slab25DLayer:
     """denseunet3d.py:399-410: slab k = CT slices (k-1,k,k+1), edges replicated, as the channels of 2D sample k."""
 
-    def __init__(self, ctx, vol, out):
-        self.vol, self.out = vol, out
+    def __init__(self, ctx, vol, out, batch=1):
+        self.vol, self.out, self.batch = vol, out, batch      # batch > 1: that many volumes back to back, slabs per volume
         ctx.fwd.append(self.forward)
 
     def forward(self):
         a = self.out.act
-        ops.slab25d(self.vol, a.N, a.H, a.W, a)
+        if self.batch == 1:
+            ops.slab25d(self.vol, a.N, a.H, a.W, a)
+        else:
+            ops.slab25d_batched(self.vol, self.batch, a.N // self.batch, a.H, a.W, a)
 
 
 class Input3DLayer:
@@ -251,19 +254,22 @@ class Input3DLayer:
             ops.make_input3d_bwd(self.out.grad, self.scale, self.logits2d.grad, acc)
 
 
-def as3d(ctx, v2d):
-    """view a 2D-branch tensor [D][1][H][W][C] as the 3D tensor [1][D][H][W][C] (same memory: the reference's
+def as3d(ctx, v2d, batch=1):
+    """view a 2D-branch tensor [batch*D][1][H][W][C] as the 3D tensor [batch][D][H][W][C] (same memory: the reference's
     slice2d / transpose / concat chain, denseunet3d.py:371-420, is a pure re-indexing in depth-major layout)."""
     a = v2d.act
-    act = ops.Act(a.buf, a.off, 1, a.N, a.H, a.W, a.C, a.ld, a.dtype)
+    act = ops.Act(a.buf, a.off, batch, a.N // batch, a.H, a.W, a.C, a.ld, a.dtype)
     return Var(ctx, act, v2d.root, v2d.c0)
 
 
-def build_hybrid(ctx, vol, D, H, W, variant="3dpart", nb_layers2d=(6, 12, 36, 24), nb_layers3d=(3, 4, 12, 8)):
-    """vol: float32 device tensor [D][H][W].  Returns logits Var [1][D][H][W][cpad(3)]."""
+def build_hybrid(ctx, vol, D, H, W, variant="3dpart", nb_layers2d=(6, 12, 36, 24), nb_layers3d=(3, 4, 12, 8), batch=1):
+    """vol: float32 device tensor [batch][D][H][W].  Returns logits Var [batch][D][H][W][cpad(3)].  batch > 1 runs that many
+    independent volumes (the windows of a sliding-window sweep) through one forward: inference only, see keras_api.Model."""
     dt = ctx.dtype
     sharded = ctx.shard is not None and (ctx.shard.world > 1 or _FORCE_HALO())
     hl = 1 if sharded else 0
+    if batch < 1 or (batch > 1 and sharded):
+        raise ValueError("build_hybrid: batch >= 1, and batch > 1 only without a depth shard / halo")
     if sharded:
         # depth-sharded hybrid (SURVEY.md section 8e, third row): this rank holds D planes of the volume plus ONE raw CT
         # plane from each depth neighbour (`vol` has D+2 planes; Model._upload_x exchanges them, global edges replicate
@@ -277,17 +283,17 @@ def build_hybrid(ctx, vol, D, H, W, variant="3dpart", nb_layers2d=(6, 12, 36, 24
         ctx.vars.append(x2d)
         vol = vol[H * W:(D + 1) * H * W]
     else:
-        x2d = ctx.new_var(D, 1, H, W, ops.cpad(3, dt))
-        Slab25DLayer(ctx, vol, x2d)
+        x2d = ctx.new_var(batch * D, 1, H, W, ops.cpad(3, dt))
+        Slab25DLayer(ctx, vol, x2d, batch)
     ctx.grad_enabled = variant == "end2end"
     r2d = build_dense_unet_2d(ctx, x2d, variant=variant, nb_layers=nb_layers2d, materialize_feature=True)
     ctx.grad_enabled = True
-    in3d = ctx.new_var(1, D, H, W, ops.cpad(4, dt))
+    in3d = ctx.new_var(batch, D, H, W, ops.cpad(4, dt))
     if variant == "end2end":
         in3d.require_grad()
     Input3DLayer(ctx, vol, r2d["logits"], in3d)
     feat3d, bn3d = build_dense_net_3d(ctx, in3d, variant=variant, nb_layers=nb_layers3d)
-    fea2d = as3d(ctx, r2d["feat"])
+    fea2d = as3d(ctx, r2d["feat"], batch)
     fc = ConvLayer(ctx, "fianl_conv", feat3d, 64, (3, 3, 3), pad=(1, 1, 1), bn=bn3d, skip=fea2d, keras_nd=3,
                    dropout=0.1 if variant == "3dpart" else 0.3, halo=hl)
     st = StatsOp(ctx, fc.out)

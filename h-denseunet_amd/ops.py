@@ -689,8 +689,14 @@ def slab25d(vol_f32, D, H, W, out):
     check(_l.get().hdu_slab25d(out.dtype, fptr(vol_f32), D, H, W, out.ptr, out.ld, stream()), "hdu_slab25d")
 
 
+def slab25d_batched(vol_f32, B, D, H, W, out):
+    """vol_f32: B volumes [D][H][W] back to back; out: [B * D] 2D samples, the edge slabs of a volume replicate its own planes"""
+    check(_l.get().hdu_slab25d_batched(out.dtype, fptr(vol_f32), B, D, H, W, out.ptr, out.ld, stream()), "hdu_slab25d_batched")
+
+
 def make_input3d(vol_f32, logits2d, scale, out):
-    check(_l.get().hdu_make_input3d(out.dtype, fptr(vol_f32), logits2d.ptr, logits2d.ld, scale, out.D, out.H, out.W,
+    """pointwise over the out.N * out.D planes of `out` (N volumes back to back)"""
+    check(_l.get().hdu_make_input3d(out.dtype, fptr(vol_f32), logits2d.ptr, logits2d.ld, scale, out.N * out.D, out.H, out.W,
                                     out.ptr, out.ld, stream()), "hdu_make_input3d")
 
 
@@ -793,3 +799,26 @@ def sweep_accumulate(logits, plane, win_planes, z, num, starts, cursor, score, c
 def sweep_advance(cursor, nwin):
     """*cursor = min(*cursor + 1, nwin - 1)"""
     check(_l.get().hdu_sweep_advance(_i32p(cursor), nwin, stream()), "hdu_sweep_advance")
+
+
+SWEEP_MAX_BATCH = 8     # include/hdu.h HDU_SWEEP_MAX_BATCH
+
+
+def sweep_gather_batched(vol, z, plane, win_planes, starts, nwin, cursor, batch, dst, preprocess=None):
+    """slot i < batch of dst = the window of table entry *cursor * batch + i (nwin: one int32 device word, the window count)"""
+    assert vol.dtype == torch.float32 and vol.is_contiguous() and vol.numel() == z * plane
+    assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.numel() >= batch * win_planes * plane
+    lo, hi, mean = (float(v) for v in preprocess) if preprocess is not None else (0.0, 0.0, 0.0)
+    check(_l.get().hdu_sweep_gather_batched(_vp(vol), z, plane, win_planes, _i32p(starts), starts.numel(), _i32p(nwin),
+                                            _i32p(cursor), batch, 0 if preprocess is None else 1, lo, hi, mean, _vp(dst),
+                                            stream()), "hdu_sweep_gather_batched")
+
+
+def sweep_accumulate_batched(logits, plane, win_planes, z, num, starts, nwin, cursor, batch, score, count):
+    """the valid slots of step *cursor onto score / count, in slot order (the sequence of sweep_accumulate calls)"""
+    assert logits.M >= max(1, batch) * win_planes * plane
+    assert score.dtype == torch.float32 and score.is_contiguous() and score.numel() == z * plane * max(1, min(num, 3))
+    assert count.dtype == torch.float32 and count.is_contiguous() and count.numel() == z
+    check(_l.get().hdu_sweep_accumulate_batched(logits.dtype, logits.ptr, logits.ld, plane, win_planes, z, num, _i32p(starts),
+                                                starts.numel(), _i32p(nwin), _i32p(cursor), batch, _vp(score), _vp(count),
+                                                stream()), "hdu_sweep_accumulate_batched")

@@ -10,7 +10,14 @@ step
 is the same launch list for every window and is captured once into a linear hipGraph.  The weights and the moving statistics
 cannot change during a sweep: weight preparation and the batched BN fold run once per sweep, outside the graph.  Between two
 windows there is no host-to-device traffic and no host synchronisation.  On the emulator build the same four-part step runs
-eagerly from the same device tables."""
+eagerly from the same device tables.
+
+A model built with window_batch = W > 1 runs W windows per forward: the step is
+
+    hdu_sweep_gather_batched -> forward over W windows -> hdu_sweep_accumulate_batched -> hdu_sweep_advance
+
+replayed ceil(windows / W) times.  The table is padded to a multiple of W with the last start, and the window count of the
+sweep is one more device word, so that a partly filled last step adds only its valid slots."""
 import numpy as np
 import torch
 
@@ -37,7 +44,7 @@ class SweepPlan:
             raise ValueError("the sweep drives the unsharded hybrid nets with b=1 (test.py:27-29)")
         if not 1 <= num <= 3:
             raise ValueError("num: 1..3 of the 3 class scores (test.py passes 3)")
-        _, self.deps, self.rows, self.cols, _ = model.input_shape
+        self.batch, self.deps, self.rows, self.cols, _ = model.input_shape       # batch = the model's window_batch
         if z < self.cols or self.cols < 3:
             raise ValueError("volume smaller than the network window")
         if preprocess is not None:
@@ -48,11 +55,13 @@ class SweepPlan:
         self.plane = self.deps * self.rows
         dev = model.ctx.dev
         self.capacity = (self.z - self.cols) // max(1, self.cols // 4) + 2
+        self.capacity = -(-self.capacity // self.batch) * self.batch        # whole steps of `batch` windows
         self.vol = torch.zeros(self.z * self.plane, dtype=torch.float32, device=dev)
         self.score = torch.zeros((self.z, self.deps, self.rows, self.num), dtype=torch.float32, device=dev)
         self.count = torch.zeros(self.z, dtype=torch.float32, device=dev)
         self.starts = torch.zeros(self.capacity, dtype=torch.int32, device=dev)
-        self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)         # window index (batch 1) / step index
+        self.nwin = torch.zeros(1, dtype=torch.int32, device=dev)           # windows of the current sweep (batch > 1 reads it)
         self.graph = None
         self._graph_key = None
         self.captures = 0        # graph captures so far
@@ -63,6 +72,14 @@ class SweepPlan:
 
     def _step(self):
         m = self.model
+        if self.batch > 1:
+            ops.sweep_gather_batched(self.vol, self.z, self.plane, self.cols, self.starts, self.nwin, self.cursor, self.batch,
+                                     m.vol, self.preprocess)
+            m.ctx.run_forward()
+            ops.sweep_accumulate_batched(m.logits.act, self.plane, self.cols, self.z, self.num, self.starts, self.nwin,
+                                         self.cursor, self.batch, self.score.reshape(-1), self.count)
+            ops.sweep_advance(self.cursor, self.capacity // self.batch)
+            return
         ops.sweep_gather(self.vol, self.z, self.plane, self.cols, self.starts, self.cursor, m.vol, self.preprocess)
         m.ctx.run_forward()
         ops.sweep_accumulate(m.logits.act, self.plane, self.cols, self.z, self.num, self.starts, self.cursor,
@@ -107,6 +124,7 @@ class SweepPlan:
         vol = np.ascontiguousarray(np.asarray(imgs_test[:self.deps, :self.rows, :], np.float32).transpose(2, 0, 1))
         self.vol.copy_(torch.from_numpy(vol).reshape(-1))
         self.starts.copy_(torch.from_numpy(table))
+        self.nwin.fill_(nwin)
         ctx = self.model.ctx
         use_graph = not _l.is_emulator()
         ctx.learning_phase = 0
@@ -118,7 +136,7 @@ class SweepPlan:
             self.count.zero_()
             self.cursor.zero_()
             self.replays = 0
-            for _ in range(nwin):
+            for _ in range(-(-nwin // self.batch)):
                 if use_graph:
                     self.graph.replay()
                 else:

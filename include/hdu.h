@@ -46,7 +46,7 @@ const char* hdu_backend(void);
  * 4 = round 3 (hdu_zero_regions, hdu_comm_*), 5 = round 4 (hdu_profile_*, pointwise convs with a fused BN prologue on the
  * DMA path, hdu_wgrad_plan_shape / min_steps), 6 = round 6 (hdu_bn_bwd_apply_sums, bnb_relu bit 2), 7 = round 6 (hdu_split3_*), 8 = hdu_pp_* (device post-processing),
  * 10 = hdu_bn_bwd_fused_pw, hdu_colsum_fold_batched, column-sum table arguments of hdu_bn_bwd_fused / hdu_bn_bwd_apply_sums. */
-#define HDU_ABI_VERSION 10
+#define HDU_ABI_VERSION 11
 int hdu_abi_version(void);
 size_t hdu_sizeof_conv_desc(void);
 /* Launch profiler (measurement only; replaces nothing in the reference -- Keras has `verbose`, the reference was profiled with
@@ -523,6 +523,9 @@ int hdu_sgd_nesterov(float* p, float* v, const float* g, int64_t n, float lr, fl
  * vol: [D][H][W] float32 (one volume).  slab25d: out[k][h][w][0..2] = vol[clamp(k-1)], vol[k], vol[clamp(k+1)];
  * channels 3..Cpad-1 = 0. */
 int hdu_slab25d(int dtype, const float* vol, int D, int H, int W, void* out, int Cpad, void* stream);
+/* B volumes back to back, vol [B][D][H][W]: out[b*D + k] is slab k of volume b, the clamp to [0, D-1] stays inside volume b (an
+ * edge slab never sees the neighbouring volume).  B = 1 is the call above, bit for bit. */
+int hdu_slab25d_batched(int dtype, const float* vol, int B, int D, int H, int W, void* out, int Cpad, void* stream);
 /* input3d[d][h][w] = (vol, scale*logit0, scale*logit1, scale*logit2, 0...) ; logits2d is [D][H][W][ldl] */
 int hdu_make_input3d(int dtype, const float* vol, const void* logits2d, int64_t ldl, float scale, int D, int H,
                      int W, void* out, int Cpad, void* stream);
@@ -556,6 +559,28 @@ int hdu_sweep_gather(const float* vol, int z, int64_t plane, int win_planes, con
 int hdu_sweep_accumulate(int dtype, const void* logits, int64_t ldl, int64_t plane, int win_planes, int z, int num,
                          const int32_t* starts, int nwin, const int32_t* cursor, float* score, float* count, void* stream);
 int hdu_sweep_advance(int32_t* cursor, int nwin, void* stream);
+
+/* `batch` windows per forward (1 .. HDU_SWEEP_MAX_BATCH).  The table has ntable entries; step *cursor holds the entries
+ * *cursor*batch + i, i < batch, each clamped to the table and its start c0_i to [0, z - win_planes].  nwin_dev is ONE int32 device
+ * word, the window count of this sweep (not baked into a captured launch): slot i is VALID iff
+ * *cursor*batch + i < min(*nwin_dev, ntable).
+ * hdu_sweep_gather_batched: slot i of dst ([batch][win_planes*plane] float32) = the window at c0_i, as hdu_sweep_gather writes it
+ *   (head and tail per slot: a slot base is 4-byte aligned only).  Slots that are not valid still gather their clamped entry, so
+ *   the forward always runs on finite data.
+ * hdu_sweep_accumulate_batched: logits [batch*win_planes*plane][ldl].  The windows of one step overlap, so there is one thread
+ *   per score voxel: it reads the voxel's `num` scores once, adds the softmax of every valid slot that covers its plane z'
+ *   (c0_i+1 <= z' <= c0_i+win_planes-2; logits row (i*win_planes + z'-c0_i)*plane + p) in increasing i with the very expression
+ *   of hdu_softmax_accumulate, and stores once: the float sequence of that many hdu_sweep_accumulate calls.  Two valid slots
+ *   of the same start are both added.  count[z'] += the number of valid covering slots.  Voxels no valid slot covers are not
+ *   written.
+ * hdu_sweep_advance serves unchanged, with the number of steps as its bound. */
+#define HDU_SWEEP_MAX_BATCH 8
+int hdu_sweep_gather_batched(const float* vol, int z, int64_t plane, int win_planes, const int32_t* starts, int ntable,
+                             const int32_t* nwin_dev, const int32_t* cursor, int batch, int preprocess, float lo, float hi,
+                             float mean, float* dst, void* stream);
+int hdu_sweep_accumulate_batched(int dtype, const void* logits, int64_t ldl, int64_t plane, int win_planes, int z, int num,
+                                 const int32_t* starts, int ntable, const int32_t* nwin_dev, const int32_t* cursor, int batch,
+                                 float* score, float* count, void* stream);
 
 /* ------------------------------------------------------------------ per-step re-initialisation
  * The accumulators a training step adds into (epilogue statistics, fused BN-backward slot rows, the flat gradient buffer the

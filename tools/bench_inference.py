@@ -3,6 +3,11 @@
 224 x 224 x 12 windows over a synthetic 224 x 224 x D volume (funcs.sweep_scores mode="eager" against mode="graph").
 
   python tools/bench_inference.py [--z 64] [--reps 3] [--iters 20] [--tag mi355x] [--out FILE] [--phase-timeout 300]
+                                  [--window-batch 1,2,4] [--workloads predict2d,sweep]
+
+--window-batch W1,W2,...: the sweep phase is run once per value on a dense_rnn_net(window_batch=W) (W windows per forward),
+eager and captured; every record carries ms per window, slices/s and launches per window, so W = 2 and 4 are read against
+W = 1 of the same run.
 
 The parent process never touches the GPU: every (workload, dtype) phase is a fresh child under its own `timeout`, and the
 first phase that fails ends the run.  Inside a phase eager and captured are timed in the same process, eager first; every
@@ -75,7 +80,7 @@ def phase_predict2d(dtype, a):
     return res
 
 
-def phase_sweep(dtype, a):
+def phase_sweep(dtype, a, wb=1):
     import importlib
     import numpy as np
     import torch
@@ -85,12 +90,13 @@ def phase_sweep(dtype, a):
     torch.cuda.set_device(0)
     f, sweep = U.pkg("funcs"), U.pkg("sweep")
     args = U.make_args(1, 224, 12)
-    m = U.pkg("hybridnet").dense_rnn_net(args, dtype=dtype)
+    m = U.pkg("hybridnet").dense_rnn_net(args, dtype=dtype, window_batch=wb)
     vol = np.random.default_rng(1).normal(0.0, 40.0, (224, 224, a.z)).astype(np.float32)
     mini, maxi = (0, 0, 0), (223, 223, a.z - 1)
     nwin = len(sweep.window_starts(a.z, 12, mini, maxi))
     sync = torch.cuda.synchronize
-    res = {"workload": "sweep", "dtype": dtype, "volume": [224, 224, a.z], "window": [224, 224, 12], "windows": nwin}
+    res = {"workload": "sweep", "dtype": dtype, "window_batch": wb, "volume": [224, 224, a.z], "window": [224, 224, 12],
+           "windows": nwin, "steps": -(-nwin // wb)}
 
     def eager():
         return f.sweep_scores(m, vol, 3, mini, maxi, args)
@@ -108,7 +114,8 @@ def phase_sweep(dtype, a):
     ctx.learning_phase = 0
     try:
         plan.prepare()
-        res["launches_per_window_graph"] = _launches(lib, plan._step)             # kernel nodes of the replayed graph
+        # kernel nodes of the replayed graph (one step = window_batch windows), over the windows of the sweep
+        res["launches_per_window_graph"] = round(_launches(lib, plan._step) * res["steps"] / nwin, 1)
     finally:
         ctx.end_prefold()
         ctx.learning_phase = 1
@@ -135,23 +142,25 @@ def main():
     ap.add_argument("--tag", default="mi355x")
     ap.add_argument("--phase-timeout", type=int, default=300)
     ap.add_argument("--dtypes", default="bf16,f32")
+    ap.add_argument("--window-batch", default="1", help="windows per forward of the sweep phase, e.g. 1,2,4")
+    ap.add_argument("--workloads", default="predict2d,sweep")
     ap.add_argument("--out", default=None, help="result file (default profiles/inference_<tag>.json)")
     ap.add_argument("--phase", default=None, help="internal: run ONE phase in this process, e.g. sweep:bf16")
     a = ap.parse_args()
     if a.phase is not None:
-        name, dtype = a.phase.split(":")
-        print("PHASE_RESULT " + json.dumps(PHASES[name](dtype, a)))
+        name, dtype, wb = (a.phase.split(":") + ["1"])[:3]
+        print("PHASE_RESULT " + json.dumps(PHASES[name](dtype, a, int(wb)) if name == "sweep" else PHASES[name](dtype, a)))
         return 0
     out = {"tool": "tools/bench_inference.py", "reps": a.reps, "phases": []}
     for dtype in a.dtypes.split(","):
-        for name in ("predict2d", "sweep"):
+        for name, wb in [(n, w) for n in a.workloads.split(",") for w in (a.window_batch.split(",") if n == "sweep" else ["1"])]:
             cmd = ["timeout", "-k", "10", str(a.phase_timeout), sys.executable, os.path.abspath(__file__), "--phase",
-                   "%s:%s" % (name, dtype), "--z", str(a.z), "--reps", str(a.reps), "--iters", str(a.iters)]
+                   "%s:%s:%s" % (name, dtype, wb), "--z", str(a.z), "--reps", str(a.reps), "--iters", str(a.iters)]
             p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
             line = [ln for ln in p.stdout.splitlines() if ln.startswith("PHASE_RESULT ")]
             if p.returncode != 0 or not line:
                 sys.stderr.write(p.stdout[-4000:])
-                sys.stderr.write("\nphase %s:%s ended with status %d: nothing more is started on the GPU\n" % (name, dtype, p.returncode))
+                sys.stderr.write("\nphase %s:%s:%s ended with status %d: nothing more is started on the GPU\n" % (name, dtype, wb, p.returncode))
                 return 1
             out["phases"].append(json.loads(line[-1][len("PHASE_RESULT "):]))
     path = a.out or os.path.join(ROOT, "profiles", "inference_%s.json" % a.tag)
