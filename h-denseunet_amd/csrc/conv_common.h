@@ -51,6 +51,9 @@ struct ConvK {
   // split-K (ring kernel): gridDim.z workgroups share one output tile; partial accumulators meet in sk_ws
   float* sk_ws;               // [tile][split][wave][fragment][lane] f32x4, write-through stores
   unsigned* sk_cnt;           // [tile] arrival tickets, zero between launches
+  // second, 2 x 2 down-sampled output of the halo-wide kernels (hdu_conv_desc.y_ds): the up-sampling gradient in the epilogue
+  void* y_ds; long long ldy_ds;
+  int ds_accumulate, ds_only;
   long long M_layer;          // hdu_conv_desc.layer_rows (>= M): output pixels of the whole layer this launch is part of (host-side decisions only)
 };
 

@@ -52,7 +52,9 @@ template <int TH_, int NT_, int WAVES_M_, int WAVES_N_, int NS_> struct HaloWide
   static constexpr int ROWB = BN * 2 + 16;                 // staged output row (+16 B: consecutive rows start on different banks)
   static constexpr int SMEM = NS * STAGE > BM * ROWB ? NS * STAGE : BM * ROWB;
   static constexpr int MT = TH / WAVES_M, NTW = NT / WAVES_N;   // 32 x 32 fragments per wave: tile rows x channel groups
+  static constexpr bool DS = true;                         // the epilogue can form the 2 x 2 down-sampled second output (ConvK::y_ds)
   static_assert(TH % WAVES_M == 0 && NT % WAVES_N == 0, "wave layout");
+  static_assert(TH % 2 == 0 && TW % 2 == 0, "a 2 x 2 block of the output grid lies inside one tile");
   static_assert(SMEM <= 160 * 1024, "LDS");
   static_assert((NS - 2) * LPW < 64, "vmcnt");
 };
@@ -101,6 +103,44 @@ __device__ __forceinline__ void hw_epilogue_stats(const ConvK& p, const char* sm
       mine = rl == 8 + j ? s2[j] : mine;
     }
     if (col) atomicAdd(dst + (rl < 8 ? 0 : p.Cout) + nbase + (rl & 7), mine);
+  }
+}
+
+// second output of a data gradient behind an UpSampling (0, 1, 1) (ConvK::y_ds): the 2 x 2 sums of the staged tile = the up-sampling
+// gradient of what the full-resolution store holds (the staged bf16 values), with the arithmetic of upsample_bwd_kernel: 0.f, + the
+// four children in the order (0,0), (0,1), (1,0), (1,1) in float32, (+ the old value), one rounding.  Tile origins are multiples of
+// (TH, 32) and Ho, Wo are even (fill_convk), so a block is inside the image as a whole or not at all.
+template <typename C>
+__device__ __forceinline__ void hw_epilogue_ds(const ConvK& p, const char* smem, long long mplane, int y0, int x0, int n0, int tid) {
+  typedef bf16_t T;
+  constexpr int NCC = C::BN / 8, NQ = (C::BM / 4) * NCC, NIT = (NQ + C::NTHR - 1) / C::NTHR, ROWB = C::ROWB;
+  T* __restrict__ zp = (T*)p.y_ds;
+  const long long mplane_ds = mplane >> 1;                    // (n * Do + od) * (Ho / 2)
+  const int Wd = p.Wo >> 1;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int q = tid + it * C::NTHR;
+    const int blk = q / NCC, cc = q - blk * NCC;
+    const int ty = (blk >> 4) * 2, tx = (blk & 15) * 2;       // the block's first tile pixel (16 blocks per tile row pair)
+    const int oy = y0 + ty, ox = x0 + tx, nn = n0 + cc * 8;
+    if (q >= NQ || oy >= p.Ho || ox >= p.Wo || nn >= p.Cout) continue;
+    const char* src = smem + (ty * 32 + tx) * ROWB + cc * 16;
+    float s[8], f[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s[j] = 0.f;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      Chunk<T>::unpack(*(const u32x4*)(src + ((b >> 1) * 32 + (b & 1)) * ROWB), f);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s[j] += f[j];
+    }
+    T* dst = zp + ((mplane_ds + (oy >> 1)) * Wd + (ox >> 1)) * p.ldy_ds + nn;
+    if (p.ds_accumulate) {
+      Chunk<T>::unpack(*(const u32x4*)dst, f);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s[j] += f[j];
+    }
+    *(u32x4*)dst = Chunk<T>::pack(s);
   }
 }
 
@@ -162,6 +202,9 @@ __device__ __forceinline__ void hw_epilogue(const ConvK& p, f32x16 (&acc)[C::MT]
     }
   }
   __syncthreads();
+  if constexpr (C::DS) {
+    if (p.y_ds) hw_epilogue_ds<C>(p, smem, mplane, y0, x0, n0, tid);
+  }
   T* __restrict__ yp = (T*)p.y;
   constexpr int NCC = BN / 8;
   constexpr int NIT = (BM * NCC + NTHR - 1) / NTHR;
@@ -172,7 +215,9 @@ __device__ __forceinline__ void hw_epilogue(const ConvK& p, f32x16 (&acc)[C::MT]
     ok = q < BM * NCC && oy < p.Ho && ox < p.Wo && nn < p.Cout;
     return ok ? yp + ((mplane + oy) * p.Wo + ox) * p.ldy + nn : yp;
   };
-  if (p.accumulate) {
+  if (C::DS && p.ds_only) {
+    // the full-resolution tile exists in LDS only: nothing reads it but the 2 x 2 sums
+  } else if (p.accumulate) {
 #pragma unroll 1
     for (int it0 = 0; it0 < NIT; it0 += 4) {
       u32x4 old[4];
@@ -395,6 +440,7 @@ struct StemCfg {
   static constexpr int ROWB = BN * 2 + 16;
   static constexpr int SMEM = NS * STAGE > BM * ROWB ? NS * STAGE : BM * ROWB;
   static constexpr int MT = 2, NTW = 3;
+  static constexpr bool DS = false;                         // (a stride-2 forward layer: no down-sampled second output)
   static_assert(SMEM <= 160 * 1024, "LDS");
 };
 
@@ -800,7 +846,7 @@ static int hw_choose(const ConvK& k, int dtype) {
 
 // the stem kernels' geometry: 7 x 7 (x 7), stride 2 in the plane (and in depth for 7 x 7 x 7), 8 stored channels, plain launch
 static bool stem_geom_ok(const ConvK& k, int dtype) {
-  if (g_tuning[HDU_TUNE_HALO_WIDE] == 1 || dtype != HDU_BF16) return false;
+  if (g_tuning[HDU_TUNE_HALO_WIDE] == 1 || dtype != HDU_BF16 || k.y_ds != nullptr) return false;
   if (k.bnb_u != nullptr || k.pro_a != nullptr || k.skip != nullptr || !k.vec_out || (k.ud | k.uh | k.uw) != 0) return false;
   if (k.KH != 7 || k.KW != 7 || k.sh != 2 || k.sw != 2 || k.ph != 3 || k.pw != 3 || k.Cin != 8) return false;
   if (!((k.KD == 1 && k.sd == 1 && k.pd == 0) || (k.KD == 7 && k.sd == 2 && k.pd >= 0 && k.pd <= 3))) return false;

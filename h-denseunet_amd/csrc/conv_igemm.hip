@@ -3177,6 +3177,17 @@ static int fill_convk(const hdu_conv_desc* d, ConvK* k, bool wgrad, bool exact_g
   if (((uintptr_t)k->bias | (uintptr_t)k->epi_a | (uintptr_t)k->epi_b | (uintptr_t)(k->stats_partial ? k->stats_shift : nullptr) |
        (uintptr_t)k->bnb_a | (uintptr_t)k->bnb_b | (uintptr_t)k->bnb_mean | (uintptr_t)k->bnb_rstd) & 15)
     return hdu_set_error(HDU_ERR_ARG, "conv: bias / epi_* / stats_shift / bnb_* vectors must be 16-byte aligned");
+  k->y_ds = wgrad ? nullptr : d->y_ds; k->ldy_ds = d->ldy_ds;
+  k->ds_accumulate = d->ds_accumulate; k->ds_only = d->ds_only;
+  if (k->y_ds) {
+    if ((d->Ho | d->Wo) & 1) return hdu_set_error(HDU_ERR_ARG, "conv: the down-sampled output needs even Ho and Wo");
+    if ((uintptr_t)k->y_ds % 16 || k->ldy_ds % ch || k->ldy_ds < d->Cout)
+      return hdu_set_error(HDU_ERR_ARG, "conv: y_ds must be 16-byte aligned and ldy_ds a multiple of the 16-byte chunk >= Cout");
+    if (d->accumulate) return hdu_set_error(HDU_ERR_ARG, "conv: the down-sampled output excludes accumulate (it sums what a plain store holds)");
+    if (exact_grid) return hdu_set_error(HDU_ERR_ARG, "conv: the down-sampled output is a halo-wide hdu_conv_fprop epilogue only");
+  } else if (!wgrad && (d->ds_only || d->ds_accumulate)) {
+    return hdu_set_error(HDU_ERR_ARG, "conv: ds_only / ds_accumulate without y_ds");
+  }
   k->M_layer = d->layer_rows > 0 ? d->layer_rows : k->M;
   k->sk_ws = wgrad ? nullptr : (float*)d->splitk_ws;
   k->sk_cnt = wgrad ? nullptr : d->splitk_counters;
@@ -3507,6 +3518,8 @@ extern "C" int hdu_conv_fprop(const hdu_conv_desc* d, void* stream) {
   if (int e = fill_convk(d, &k, false)) return e;
   if (!d->y) return hdu_set_error(HDU_ERR_ARG, "conv_fprop: null output");
   if (k.M == 0) return 0;
+  if (k.y_ds && !hdu_halo_wide_taken(k, d->dtype))      // (only the halo-wide epilogue forms it: never a silently missing output)
+    return hdu_set_error(HDU_ERR_ARG, "conv_fprop: y_ds needs a launch that a halo-wide configuration takes");
   if (pw_bstat_ok(k, d->dtype)) {
     launch_pw_bstat(k, (hipStream_t)stream);
     return hdu_check_launch("conv_fprop(pointwise, filter-stationary)");

@@ -198,6 +198,9 @@ class Ctx:
         self.fuse_bn_bwd = self.fuse_bn_bwd_mode > 0
         self.fuse_bn_bwd_pw = os.environ.get("HDU_FUSE_BN_BWD_PW", "1") == "1"
         self.bnb_sums_epilogue = os.environ.get("HDU_BNB_SUMS_EPILOGUE", "1") == "1"      # round 6: ConvLayer._epilogue_sums
+        # the gradient of an in-plane UpSampling in front of a conv is summed by the epilogue of the halo-wide data-gradient launch
+        # (hdu_conv_desc.y_ds: ConvLayer._ups_epilogue); 0 = the full-resolution store + hdu_upsample_bwd reading it back
+        self.ups_bwd_epilogue = os.environ.get("HDU_UPS_BWD_EPILOGUE", "1") == "1"
         # a segmentation head (pointwise conv, <= 4 classes in one stored chunk) behind a BN: the BN backward forms dz = dy . W in
         # registers (hdu_bn_bwd_fused_pw) -- no data-gradient launch, no stored dz (ConvLayer._head_dz_fused); 0 = the three launches
         self.head_dz_fused = os.environ.get("HDU_HEAD_DZ_FUSED", "1") == "1"
@@ -950,6 +953,7 @@ class ConvLayer:
                               and (ctx.fuse_bn_bwd_mode >= 2 or bn.mode != "batch" or pw_stream))
         self.bnb_off = None
         self._sums_kernel_ok = None       # does this layer's data gradient run on a tile kernel that can take the BN sums? (_epilogue_sums)
+        self._ups_kernel_ok = None        # ... on a halo-wide kernel, whose epilogue can sum the up-sampling gradient? (_ups_epilogue)
         self._s2 = None
         self._s2_ok = (os.environ.get("HDU_STRIDE2_DGRAD", "1") == "1" and all(v in (1, 2) for v in stride)
                        and xa.D % stride[0] == 0 and xa.H % stride[1] == 0 and xa.W % stride[2] == 0 and up == (0, 0, 0)
@@ -1133,7 +1137,12 @@ class ConvLayer:
             d = ctx.conv_desc(dy, self.wd_ptr, ops.Act(tgt.buf, tgt.off, x.N, De, He, We, x.C, tgt.ld, tgt.dtype), K,
                               (1, 1, 1), (K[0] - 1 - pad[0], K[1] - 1 - pad[1], K[2] - 1 - pad[2]), accumulate=acc)
             sums_ready = self._epilogue_sums(d)
+            ups_dz = self._ups_epilogue(d, direct, skip_first, acc)
             ops.conv_fprop(d)
+            if ups_dz is not None:      # the launch wrote the up-sampling gradient too (and d(x_eff) only where the skip needs it)
+                if self.bn is not None:
+                    self.bn.backward(self.x, ups_dz, sums_ready=sums_ready)
+                return
         if self.skip is not None and self.skip.root.needs_grad and not skip_first:
             # generic fallback: add d(x_eff) into an already-written skip gradient
             ops.upsample_bwd(tgt, self.skip.grad, (0, 0, 0), accumulate=self.skip.grad_mode())
@@ -1171,6 +1180,33 @@ class ConvLayer:
                     and self.cout_p == ops.CHUNK[ctx.dtype] and self.filters <= 4 and self.wd_ptr is not None
                     and self.wd_ptr.value % 16 == 0 and self.out.grad.ptr.value % 16 == 0
                     and not (ctx.shard is not None and ctx.shard.world > 1) and bn.takes_epilogue_sums(self.x))
+
+    def _ups_epilogue(self, d, direct, skip_first, acc):
+        """The gradient of the in-plane UpSampling (0, 1, 1) in front of this conv -- the 2 x 2 sums of d(x_eff) -- is formed by the
+        epilogue of the data-gradient launch `d` from its staged output tile (hdu_conv_desc.y_ds) instead of by hdu_upsample_bwd
+        reading the full-resolution tensor back.  Taken when d(x_eff) goes to the scratch tensor (then it is not stored at all:
+        ds_only) or, as a plain store, to a skip gradient nobody wrote yet (then both outputs), and the launch runs on a halo-wide
+        kernel (decided once from the kernel the plain descriptor picks).  The sums go to the dz scratch when a BN follows, into
+        x.grad otherwise.  Bit-identical to the three-launch form.  HDU_UPS_BWD_EPILOGUE=0: off.  Returns dz's Act, or None."""
+        ctx = self.ctx
+        if not ctx.ups_bwd_epilogue or direct or self.up != (0, 1, 1) or self.halo or ctx.dtype != HDU_BF16:
+            return None
+        if self.skip is not None and self.skip.root.needs_grad and not skip_first:
+            return None               # the generic fallback adds d(x_eff) into a written skip gradient: it has to exist
+        if skip_first and acc:
+            return None
+        if self._ups_kernel_ok is None:
+            self._ups_kernel_ok = ops.conv_kernel_name(d, 0).startswith("conv_halo_wide_kernel")
+        if not self._ups_kernel_ok:
+            return None
+        if self.bn is not None:
+            dz, dacc = self._dz(), False
+        else:
+            dz, dacc = self.x.grad, self.x.grad_mode()
+        d.y_ds, d.ldy_ds = dz.ptr, dz.ld
+        d.ds_accumulate = 1 if dacc else 0
+        d.ds_only = 0 if skip_first else 1
+        return dz
 
     def _epilogue_sums(self, d):
         """Round 6: the backward sums of this conv's input BN (S1 = sum g, S2 = sum g * uhat) ride in the

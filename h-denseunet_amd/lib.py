@@ -50,6 +50,9 @@ class ConvDesc(ctypes.Structure):
         ("splitk_ws_bytes", c_sz),
         ("splitk_counters", c_p),
         ("layer_rows", ctypes.c_int64),
+        ("y_ds", c_p), ("ldy_ds", c_i64),
+        ("ds_accumulate", c_int),
+        ("ds_only", c_int),
     ]
 
 
@@ -224,7 +227,7 @@ class HduError(RuntimeError):
     pass
 
 
-ABI_VERSION = 11       # include/hdu.h HDU_ABI_VERSION
+ABI_VERSION = 12       # include/hdu.h HDU_ABI_VERSION
 
 
 def product_library_path():

@@ -45,8 +45,9 @@ const char* hdu_backend(void);
  * refuses a stale library (h-denseunet_amd/lib.py does): 1 = round 1, 2 = round 2 (splitk_*, bnb_*), 3 = epi_*,
  * 4 = round 3 (hdu_zero_regions, hdu_comm_*), 5 = round 4 (hdu_profile_*, pointwise convs with a fused BN prologue on the
  * DMA path, hdu_wgrad_plan_shape / min_steps), 6 = round 6 (hdu_bn_bwd_apply_sums, bnb_relu bit 2), 7 = round 6 (hdu_split3_*), 8 = hdu_pp_* (device post-processing),
- * 10 = hdu_bn_bwd_fused_pw, hdu_colsum_fold_batched, column-sum table arguments of hdu_bn_bwd_fused / hdu_bn_bwd_apply_sums. */
-#define HDU_ABI_VERSION 11
+ * 10 = hdu_bn_bwd_fused_pw, hdu_colsum_fold_batched, column-sum table arguments of hdu_bn_bwd_fused / hdu_bn_bwd_apply_sums,
+ * 12 = y_ds / ldy_ds / ds_accumulate / ds_only (the up-sampling gradient in the halo-wide data-gradient epilogue). */
+#define HDU_ABI_VERSION 12
 int hdu_abi_version(void);
 size_t hdu_sizeof_conv_desc(void);
 /* Launch profiler (measurement only; replaces nothing in the reference -- Keras has `verbose`, the reference was profiled with
@@ -184,6 +185,17 @@ typedef struct hdu_conv_desc {
    * and split-K decisions are then taken for that pixel count, so every output element is summed over the same K partition
    * -- bit for bit -- as in the unsharded launch.  0 = this launch is the whole layer. */
   int64_t layer_rows;
+  /* optional second output (ABI 12; hdu_conv_fprop, halo-wide kernels only): the 2 x 2 in-plane sums of the output tile over the
+   * grid (N, Do, Ho >> 1, Wo >> 1, Cout) with pixel stride ldy_ds -- the gradient of a nearest-neighbour UpSampling (0, 1, 1) in
+   * front of the conv whose data gradient this launch is, formed from the staged tile instead of by hdu_upsample_bwd reading
+   * `y` back.  Per element: 0.f + the four stored (rounded) values of `y` in the order (0,0), (0,1), (1,0), (1,1), in float32,
+   * (+ the old value with ds_accumulate), rounded once: bit for bit what hdu_upsample_bwd(y -> y_ds, ud = 0, uh = uw = 1) gives.
+   * ds_only != 0: `y` is not written at all (it still must be non-NULL and describes the full-resolution grid).
+   * Needs even Ho and Wo, a 16-byte aligned y_ds, ldy_ds a multiple of the chunk and accumulate == 0; a launch that no halo-wide
+   * configuration takes is an error, never a silently missing output. */
+  void* y_ds;         int64_t ldy_ds;
+  int ds_accumulate;
+  int ds_only;
 } hdu_conv_desc;
 
 /* finishes the sums of a fused BN-backward epilogue (hdu_conv_desc.bnb_partial): S1, S2 totals -> parameter gradients
