@@ -5,6 +5,8 @@
 // chunks (8 bf16 / 4 f32) so a wavefront touches contiguous 1 KiB runs whenever C allows it.
 #include "hdu_host.h"
 
+#include <stdio.h>
+
 // ====================================================================== per-channel reductions
 enum { RED_STATS = 0, RED_BNBWD = 1, RED_COLSUM = 2 };
 enum { ROW_UNROLL = 4 };   // rows of loads each thread of a row kernel keeps in flight
@@ -2339,6 +2341,127 @@ __global__ void sweep_advance_kernel(int* cursor, int nwin) {
   }
 }
 
+// ------------------------------------------------------------------ tiled 3-D window step (include/hdu.h: hdu_tile_*)
+// lib/funcs.py:54-129 tiles the volume in all three axes.  The table holds one (x0, y0, z0) per tile; slot i of step *cursor is
+// entry *cursor * batch + i, clamped to the table, and its start to [0, X-deps] x [0, Y-rows] x [0, Z-cols].
+struct TileStart { int x0, y0, z0; };
+__device__ __forceinline__ TileStart tile_slot_start(const int* __restrict__ starts, int ntable, long long entry, int X, int Y, int Z,
+                                                     int deps, int rows, int cols) {
+  const int w = entry < 0 ? 0 : (entry >= ntable ? ntable - 1 : (int)entry);
+  const int x0 = starts[3 * w], y0 = starts[3 * w + 1], z0 = starts[3 * w + 2];
+  TileStart t;
+  t.x0 = x0 < 0 ? 0 : (x0 > X - deps ? X - deps : x0);
+  t.y0 = y0 < 0 ? 0 : (y0 > Y - rows ? Y - rows : y0);
+  t.z0 = z0 < 0 ? 0 : (z0 > Z - cols ? Z - cols : z0);
+  return t;
+}
+
+// element j = (k * deps + d) * rows + r of a tile -> its offset in the resident volume [Z][X][Y]
+__device__ __forceinline__ long long tile_src_offset(long long j, const TileStart& t, int X, int Y, int deps, int rows) {
+  const int r = (int)(j % rows);
+  const long long kd = j / rows;
+  const int d = (int)(kd % deps), k = (int)(kd / deps);
+  return ((long long)(t.z0 + k) * X + (t.x0 + d)) * Y + (t.y0 + r);
+}
+
+// slot blockIdx.y: dst[slot][k][d][r] = pre(vol[z0+k][x0+d][y0+r]).  The slot is contiguous (16-byte stores between a scalar
+// head and tail); a source row is `rows` floats at a base that is only 4-byte aligned in general, so a four-float group is
+// one 16-byte load only where it lies in one source row and that address is aligned, four scalar loads otherwise.
+__global__ __launch_bounds__(256) void tile_gather_batched_kernel(const float* __restrict__ vol, int X, int Y, int Z, int deps,
+                                                                  int rows, int cols, const int* __restrict__ starts, int ntable,
+                                                                  const int* __restrict__ cursor, int batch, int pre, float lo,
+                                                                  float hi, float mean, float* __restrict__ dst0) {
+  const int slot = blockIdx.y;
+  const TileStart t = tile_slot_start(starts, ntable, (long long)*cursor * batch + slot, X, Y, Z, deps, rows, cols);
+  const long long n = (long long)cols * deps * rows;
+  float* __restrict__ dst = dst0 + slot * n;
+  long long head = (long long)(((16u - (unsigned)((uintptr_t)dst & 15u)) & 15u) >> 2);
+  if (head > n) head = n;
+  const long long n4 = (n - head) >> 2;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    const long long j = head + 4 * i;
+    const float* s = vol + tile_src_offset(j, t, X, Y, deps, rows);
+    f32x4 v;
+    if ((int)(j % rows) + 3 < rows) {
+      if (((uintptr_t)s & 15u) == 0) v = *(const f32x4*)s;
+      else v = f32x4{s[0], s[1], s[2], s[3]};
+    } else {
+      v = f32x4{s[0], vol[tile_src_offset(j + 1, t, X, Y, deps, rows)], vol[tile_src_offset(j + 2, t, X, Y, deps, rows)],
+                vol[tile_src_offset(j + 3, t, X, Y, deps, rows)]};
+    }
+    if (pre) v = f32x4{sweep_pre(v.x, 1, lo, hi, mean), sweep_pre(v.y, 1, lo, hi, mean), sweep_pre(v.z, 1, lo, hi, mean),
+                       sweep_pre(v.w, 1, lo, hi, mean)};
+    *(f32x4*)(dst + j) = v;
+  }
+  if (blockIdx.x == 0) {
+    for (long long j = threadIdx.x; j < head; j += 256)
+      dst[j] = sweep_pre(vol[tile_src_offset(j, t, X, Y, deps, rows)], pre, lo, hi, mean);
+    for (long long j = head + 4 * n4 + threadIdx.x; j < n; j += 256)
+      dst[j] = sweep_pre(vol[tile_src_offset(j, t, X, Y, deps, rows)], pre, lo, hi, mean);
+  }
+}
+
+// ONE slot of the step onto score [Z][X][Y][num]: one thread per tile voxel, softmax3_add of its logits row onto zeros, then
+// `+=`.  The tiles of a step overlap each other, so every slot is a launch of its own and stream order sequences the `+=` of a
+// voxel in tile order (lib/funcs.py:122-123); a launch whose slot is not valid returns at once.
+template <typename T>
+__global__ __launch_bounds__(256) void tile_accumulate_kernel(const T* __restrict__ logits, long long ldl, int X, int Y, int Z,
+                                                              int deps, int rows, int cols, int num,
+                                                              const int* __restrict__ starts, int ntable,
+                                                              const int* __restrict__ ntiles_dev, const int* __restrict__ cursor,
+                                                              int batch, int slot, float* __restrict__ score) {
+  const long long entry = (long long)*cursor * batch + slot;
+  int nt = *ntiles_dev;
+  nt = nt < ntable ? nt : ntable;
+  if (entry >= nt) return;
+  const TileStart t = tile_slot_start(starts, ntable, entry, X, Y, Z, deps, rows, cols);
+  const long long n = (long long)cols * deps * rows;
+  const T* __restrict__ lg = logits + slot * n * ldl;
+  for (long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x; m < n; m += (long long)gridDim.x * blockDim.x) {
+    // the softmax first, rounded to float32 as hdu_softmax_accumulate leaves it on a zeroed buffer, then the reference's
+    // `score[...] += patch_test_mask[i]`: two roundings, where adding straight onto the score may contract into one fma
+#pragma clang fp contract(off)
+    float p[3] = {0.f, 0.f, 0.f};
+    softmax3_add(lg + m * ldl, num, p);
+    float* __restrict__ o = score + tile_src_offset(m, t, X, Y, deps, rows) * num;
+    o[0] += p[0];
+    if (num > 1) o[1] += p[1];
+    if (num > 2) o[2] += p[2];
+  }
+}
+
+// score [Z][X][Y][num] -> the host's raster order [X][Y][Z]: out_score = score[..][channel] / (cx[x] * cy[y] * cz[z]) (the tile
+// set is a Cartesian product, so the coverage count of a voxel is the product of three per-axis counts), out_mask = the
+// threshold of that value compared in double (as pp_threshold_kernel compares).  For one x, a 64 (y) x 64 (z) tile goes
+// through LDS: the read runs along y, the write along z; a row pitch of 65 words keeps both phases off shared banks (64 banks
+// of 4 bytes: lane l of the read phase touches bank (zl * 65 + l) % 64, of the write phase (l * 65 + yl) % 64).
+__global__ __launch_bounds__(256) void tile_finalize_kernel(const float* __restrict__ score, int X, int Y, int Z, int num,
+                                                            int channel, const float* __restrict__ cx,
+                                                            const float* __restrict__ cy, const float* __restrict__ cz,
+                                                            double thres, float* __restrict__ out_score,
+                                                            uint8_t* __restrict__ out_mask) {
+  __shared__ float tile[64][65];
+  const int x = blockIdx.x, y0 = blockIdx.y * 64, z0 = blockIdx.z * 64;
+  const int tid = threadIdx.x;
+  const float nx = cx[x];
+  for (int k = 0; k < 16; ++k) {
+    const int e = k * 256 + tid, zl = e >> 6, yl = e & 63;
+    const int y = y0 + yl, z = z0 + zl;
+    if (y >= Y || z >= Z) continue;
+    tile[zl][yl] = score[(((size_t)z * X + x) * Y + y) * num + channel] / (nx * cy[y] * cz[z]);     // float32, IEEE division
+  }
+  __syncthreads();
+  for (int k = 0; k < 16; ++k) {
+    const int e = k * 256 + tid, yl = e >> 6, zl = e & 63;
+    const int y = y0 + yl, z = z0 + zl;
+    if (y >= Y || z >= Z) continue;
+    const float s = tile[zl][yl];
+    const size_t o = ((size_t)x * Y + y) * Z + z;
+    if (out_score) out_score[o] = s;
+    if (out_mask) out_mask[o] = (double)s >= thres ? 1 : 0;
+  }
+}
+
 #define HDU_T_LAUNCH(T, kern, n, ...) \
   HDU_LAUNCH((kern<T>), dim3(hdu_grid_1d((n), 256, 4096)), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__)
 #define HDU_CHECK_DTYPE(what) \
@@ -2465,6 +2588,73 @@ extern "C" int hdu_sweep_accumulate_batched(int dtype, const void* logits, int64
   if (dtype == HDU_BF16) { HDU_T_LAUNCH(bf16_t, sweep_accumulate_batched_kernel, M, (const bf16_t*)logits, (long long)ldl, (long long)plane, win_planes, z, num, (const int*)starts, ntable, (const int*)nwin_dev, (const int*)cursor, batch, score, count); }
   else { HDU_T_LAUNCH(float, sweep_accumulate_batched_kernel, M, (const float*)logits, (long long)ldl, (long long)plane, win_planes, z, num, (const int*)starts, ntable, (const int*)nwin_dev, (const int*)cursor, batch, score, count); }
   return hdu_check_launch("sweep_accumulate_batched");
+}
+
+#define HDU_STR_(x) #x
+#define HDU_STR(x) HDU_STR_(x)
+
+// what every hdu_tile_* entry point asks of the volume, the tile and the table
+static const char* tile_geometry_error(int X, int Y, int Z, int deps, int rows, int cols, int ntable, int batch) {
+  if (deps < 3 || rows < 3 || cols < 3) return "tile dims must be >= 3";
+  if (X < deps || Y < rows || Z < cols) return "the volume must hold one tile in every axis";
+  if ((long long)X * Y * Z >= 0xFFFFFFFFll) return "volumes of 2^32 - 1 voxels or more are not supported";
+  if (ntable < 1) return "ntable >= 1";
+  if (batch < 1 || batch > HDU_SWEEP_MAX_BATCH) return "batch in 1.." HDU_STR(HDU_SWEEP_MAX_BATCH);
+  return nullptr;
+}
+
+extern "C" int hdu_tile_gather_batched(const float* vol, int X, int Y, int Z, int deps, int rows, int cols, const int32_t* starts,
+                                       int ntable, const int32_t* ntiles_dev, const int32_t* cursor, int batch, int preprocess,
+                                       float lo, float hi, float mean, float* dst, void* stream) {
+  // ntiles_dev is checked and then not read: a slot past the tile count is gathered all the same (include/hdu.h)
+  if (!vol || !starts || !ntiles_dev || !cursor || !dst) return hdu_set_error(HDU_ERR_ARG, "tile_gather_batched: null pointer");
+  if (const char* why = tile_geometry_error(X, Y, Z, deps, rows, cols, ntable, batch)) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "tile_gather_batched: bad args (%s)", why);
+    return hdu_set_error(HDU_ERR_ARG, msg);
+  }
+  if (((uintptr_t)vol & 3) || ((uintptr_t)dst & 3) || ((uintptr_t)starts & 3) || ((uintptr_t)ntiles_dev & 3) || ((uintptr_t)cursor & 3))
+    return hdu_set_error(HDU_ERR_ARG, "tile_gather_batched: float32 / int32 buffers must be 4-byte aligned");
+  if (preprocess && !(lo <= hi)) return hdu_set_error(HDU_ERR_ARG, "tile_gather_batched: preprocessing needs lo <= hi");
+  const long long n = (long long)cols * deps * rows;
+  HDU_LAUNCH(tile_gather_batched_kernel, dim3(hdu_grid_1d((n + 3) / 4, 256, 4096), batch), dim3(256), 0, (hipStream_t)stream, vol,
+             X, Y, Z, deps, rows, cols, (const int*)starts, ntable, (const int*)cursor, batch, preprocess ? 1 : 0, lo, hi, mean,
+             dst);
+  return hdu_check_launch("tile_gather_batched");
+}
+
+extern "C" int hdu_tile_accumulate(int dtype, const void* logits, int64_t ldl, int X, int Y, int Z, int deps, int rows, int cols,
+                                   int num, const int32_t* starts, int ntable, const int32_t* ntiles_dev, const int32_t* cursor,
+                                   int batch, int slot, float* score, void* stream) {
+  if (!logits || !starts || !ntiles_dev || !cursor || !score) return hdu_set_error(HDU_ERR_ARG, "tile_accumulate: null pointer");
+  if (const char* why = tile_geometry_error(X, Y, Z, deps, rows, cols, ntable, batch)) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "tile_accumulate: bad args (%s)", why);
+    return hdu_set_error(HDU_ERR_ARG, msg);
+  }
+  if (ldl < 3 || num < 1 || num > 3 || slot < 0 || slot >= batch)
+    return hdu_set_error(HDU_ERR_ARG, "tile_accumulate: bad args (3 classes, num in 1..3, 0 <= slot < batch)");
+  HDU_CHECK_DTYPE("tile_accumulate");
+  if (((uintptr_t)score & 3) || ((uintptr_t)starts & 3) || ((uintptr_t)ntiles_dev & 3) || ((uintptr_t)cursor & 3))
+    return hdu_set_error(HDU_ERR_ARG, "tile_accumulate: float32 / int32 buffers must be 4-byte aligned");
+  const long long n = (long long)cols * deps * rows;
+  if (dtype == HDU_BF16) { HDU_T_LAUNCH(bf16_t, tile_accumulate_kernel, n, (const bf16_t*)logits, (long long)ldl, X, Y, Z, deps, rows, cols, num, (const int*)starts, ntable, (const int*)ntiles_dev, (const int*)cursor, batch, slot, score); }
+  else { HDU_T_LAUNCH(float, tile_accumulate_kernel, n, (const float*)logits, (long long)ldl, X, Y, Z, deps, rows, cols, num, (const int*)starts, ntable, (const int*)ntiles_dev, (const int*)cursor, batch, slot, score); }
+  return hdu_check_launch("tile_accumulate");
+}
+
+extern "C" int hdu_tile_finalize(const float* score, int X, int Y, int Z, int num, int channel, const float* cx, const float* cy,
+                                 const float* cz, double thres, float* out_score, uint8_t* out_mask, void* stream) {
+  if (!score || !cx || !cy || !cz || (!out_score && !out_mask)) return hdu_set_error(HDU_ERR_ARG, "tile_finalize: null pointer");
+  if (X < 1 || Y < 1 || Z < 1 || (long long)X * Y * Z >= 0xFFFFFFFFll || num < 1 || num > 3 || channel < 0 || channel >= num)
+    return hdu_set_error(HDU_ERR_ARG, "tile_finalize: bad args (volume of 1 .. 2^32 - 2 voxels, num in 1..3, 0 <= channel < num)");
+  if (((uintptr_t)score & 3) || ((uintptr_t)cx & 3) || ((uintptr_t)cy & 3) || ((uintptr_t)cz & 3) || ((uintptr_t)out_score & 3))
+    return hdu_set_error(HDU_ERR_ARG, "tile_finalize: float32 buffers must be 4-byte aligned");
+  if ((Z + 63) / 64 > 65535 || (Y + 63) / 64 > 65535)
+    return hdu_set_error(HDU_ERR_ARG, "tile_finalize: bad args (Y and Z below 64 * 65536)");
+  HDU_LAUNCH(tile_finalize_kernel, dim3(X, (Y + 63) / 64, (Z + 63) / 64), dim3(256), 0, (hipStream_t)stream, score, X, Y, Z, num,
+             channel, cx, cy, cz, thres, out_score, out_mask);
+  return hdu_check_launch("tile_finalize");
 }
 
 // ------------------------------------------------------------------ per-step re-initialisation (include/hdu.h)

@@ -248,3 +248,107 @@ def segment_volume(model, imgs_test, liver_mask, args, thres_liver=0.5, thres_tu
     mask_dev, mini, maxi = liver_window_from_mask_device(liver_mask)
     score, score_num = sweep_scores(model, imgs_test, 3, mini, maxi, args, mode=mode, preprocess=preprocess)
     return segment_liver_tumor_device(score, score_num, shape, mask_dev, thres_liver, thres_tumor)
+
+
+# ------------------------------------------------------------------ tiled 3-D sliding-window inference (lib/funcs.py:54-153)
+# predict_window_mulgpu tiles the volume in ALL three axes with overlapping tiles (stride (t // 3) * 2 per axis, the last start
+# clamped) and averages the softmax scores; get_binary_mask / GeneSeglivertumor keep the largest component of the 0.5 mask.
+# Here the volume, the summed scores and the masks stay in HBM (sweep.TiledSweepPlan, include/hdu.h: hdu_tile_*).
+def tiled_sweep_scores(model, imgs_test, num=3, mode="eager", preprocess=None):
+    """the tile sweep of predict_window_mulgpu, left on the device: (score float32 device tensor [Z][X][Y][num] of summed
+    softmax scores, (cx, cy, cz) float32 device vectors: cx[x] * cy[y] * cz[z] tiles covered voxel (x, y, z)).  Both are the
+    plan's own buffers, valid until the next tiled sweep of this model.
+    The tile is the model's input window and `batch` its window_batch; the last, partly filled step runs too and adds only its
+    valid slots (the reference never predicts those tiles: see predict_window_mulgpu).
+    mode="eager": every step driven from the host, which sets the step cursor.  mode="graph": one captured step replayed
+    ceil(tiles / batch) times.  Both run the same launches.
+    preprocess=(lo, hi, mean): `imgs_test` is raw; the tile gather writes min(max(v, lo), hi) - mean."""
+    if mode not in ("eager", "graph"):
+        raise ValueError("mode: 'eager' or 'graph', not %r" % (mode,))
+    if model.kind != "hybrid" or model.ctx.shard_world() > 1:
+        raise ValueError("the tiled sweep drives the unsharded hybrid nets")
+    shape = tuple(int(v) for v in np.shape(imgs_test)[:3])
+    _, deps, rows, cols, _ = model.input_shape
+    if len(shape) != 3 or shape[0] < deps or shape[1] < rows or shape[2] < cols:
+        raise ValueError("volume smaller than the network window")
+    return sweep.tiled_plan_for(model, shape, num, preprocess).sweep(imgs_test, graph=(mode == "graph"))
+
+
+def _check_window_call(model, batch, imgs_test, img_deps, img_rows, img_cols, multiloss):
+    if multiloss:
+        raise ValueError("multiloss=True selects output [2] of a deep-supervision model; these models have one output")
+    if model.kind != "hybrid" or model.ctx.shard_world() > 1:
+        raise ValueError("the tiled sweep drives the unsharded hybrid nets")
+    W, deps, rows, cols, _ = model.input_shape
+    if int(batch) != W:
+        raise ValueError("batch=%d: the model was built with window_batch=%d" % (batch, W))
+    if (int(img_deps), int(img_rows), int(img_cols)) != (deps, rows, cols):
+        raise ValueError("tile %s: the model's window is %s" % ((img_deps, img_rows, img_cols), (deps, rows, cols)))
+    shape = tuple(int(v) for v in np.shape(imgs_test)[:3])
+    if len(shape) != 3 or shape[0] < deps or shape[1] < rows or shape[2] < cols:
+        raise ValueError("volume smaller than the network window (the reference dies on a broadcast error here)")
+    return shape
+
+
+def predict_window_mulgpu(model, batch, imgs_test, img_deps, img_rows, img_cols, multiloss, mode="eager", channel=1,
+                          preprocess=None):
+    """Drop-in for lib/funcs.py:54-129: the float32 (x, y, z) volume of the averaged class-`channel` softmax scores of the
+    overlapping tiles (score / score_num, no epsilon; the reference returns channel 1).
+    Deviation: the reference predicts a box only when it is full, so with a tile count that is no multiple of `batch` it never
+    runs the leftover tiles and the voxels only they cover come out NaN (0 / 0).  Here the last, partly filled step runs too:
+    every voxel is covered, and the result equals the reference's wherever that is defined (batch == 1, or a tile count that
+    is a multiple of `batch`).
+    `batch` must be the model's window_batch and the tile its input window; multiloss must be False."""
+    shape = _check_window_call(model, batch, imgs_test, img_deps, img_rows, img_cols, multiloss)
+    if not 0 <= int(channel) < 3:
+        raise ValueError("channel: 0..2")
+    score, (cx, cy, cz) = tiled_sweep_scores(model, imgs_test, 3, mode=mode, preprocess=preprocess)
+    out = torch.empty(shape, dtype=torch.float32, device=score.device)
+    ops.tile_finalize(score, shape, 3, int(channel), cx, cy, cz, out_score=out.reshape(-1))
+    return out.cpu().numpy()
+
+
+def GeneSeglivertumor(score):
+    """lib/funcs.py:138-153: `score` is thresholded IN PLACE at 0.5 (as the reference does) and the largest 26-connected
+    component of the result comes back (first label wins a tie; ValueError on an empty mask, where the reference raises on
+    max([]))."""
+    score[score >= 0.5] = 1
+    score[score < 0.5] = 0
+    return _largest_component(score)
+
+
+def get_binary_mask(score, id=None):
+    """lib/funcs.py:131-136: np.int16(GeneSeglivertumor(score)); `id` is unused there too"""
+    return np.int16(GeneSeglivertumor(score))
+
+
+def segment_tiled_scores(score, coverage, shape, thres=0.5, channel=1):
+    """get_binary_mask on the device, from the tiled sweep's own accumulators (tiled_sweep_scores): score float32 device
+    tensor [Z][X][Y][num], coverage = its (cx, cy, cz), shape = (x, y, z).  hdu_tile_finalize writes the mask only; only the
+    int16 label volume and the component count come back."""
+    shape = tuple(int(v) for v in shape)
+    num = int(score.shape[-1])
+    if not 0 <= int(channel) < num:
+        raise ValueError("channel: 0..%d" % (num - 1))
+    ws = _PostWorkspace(shape, score.device)
+    mask, out = ws.mask(), ws.mask()
+    ops.tile_finalize(score, shape, num, int(channel), *coverage, thres=thres, out_mask=mask)
+    ncomp = ws.largest26(mask, out)
+    labels = out.to(torch.int16)
+    if int(ncomp.cpu()[0]) == 0:
+        raise ValueError(_NO_COMPONENT)
+    return labels.cpu().numpy().reshape(shape)
+
+
+def segment_volume_tiled(model, imgs_test, mode="eager", thres=0.5, channel=1, preprocess=None):
+    """get_binary_mask(predict_window_mulgpu(...)) with nothing but the int16 label volume and the component count coming back
+    to the host: tiled sweep -> hdu_tile_finalize (mask only) -> largest 26-connected component on the device.  Bit-identical
+    to the host form."""
+    if model.kind != "hybrid" or model.ctx.shard_world() > 1:
+        raise ValueError("the tiled sweep drives the unsharded hybrid nets")
+    W, deps, rows, cols, _ = model.input_shape
+    shape = _check_window_call(model, W, imgs_test, deps, rows, cols, False)
+    if not 0 <= int(channel) < 3:
+        raise ValueError("channel: 0..2")
+    score, coverage = tiled_sweep_scores(model, imgs_test, 3, mode=mode, preprocess=preprocess)
+    return segment_tiled_scores(score, coverage, shape, thres, channel)

@@ -195,6 +195,11 @@ _SIGS = {
     "hdu_sweep_gather_batched": (c_int, [c_p, c_int, c_i64, c_int, c_p, c_int, c_p, c_p, c_int, c_int, c_f, c_f, c_f, c_p, c_p]),
     "hdu_sweep_accumulate_batched": (c_int, [c_int, c_p, c_i64, c_i64, c_int, c_int, c_int, c_p, c_int, c_p, c_p, c_int, c_p,
                                              c_p, c_p]),
+    "hdu_tile_gather_batched": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_int, c_p, c_p, c_int, c_int, c_f, c_f,
+                                        c_f, c_p, c_p]),
+    "hdu_tile_accumulate": (c_int, [c_int, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_int, c_p, c_p, c_int,
+                                    c_int, c_p, c_p]),
+    "hdu_tile_finalize": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, ctypes.c_double, c_p, c_p, c_p]),
     "hdu_pp_threshold": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_p, c_p, c_p]),
     "hdu_pp_dilate": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p]),
     "hdu_pp_label": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
@@ -227,7 +232,7 @@ class HduError(RuntimeError):
     pass
 
 
-ABI_VERSION = 12       # include/hdu.h HDU_ABI_VERSION
+ABI_VERSION = 13       # include/hdu.h HDU_ABI_VERSION
 
 
 def product_library_path():

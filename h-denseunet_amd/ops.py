@@ -822,3 +822,44 @@ def sweep_accumulate_batched(logits, plane, win_planes, z, num, starts, nwin, cu
     check(_l.get().hdu_sweep_accumulate_batched(logits.dtype, logits.ptr, logits.ld, plane, win_planes, z, num, _i32p(starts),
                                                 starts.numel(), _i32p(nwin), _i32p(cursor), batch, _vp(score), _vp(count),
                                                 stream()), "hdu_sweep_accumulate_batched")
+
+
+# ------------------------------------------------------------------ tiled 3-D window step (include/hdu.h: hdu_tile_*)
+# shape = (X, Y, Z) of the volume, tile = (deps, rows, cols); starts: int32 device table [ntable][3] of (x0, y0, z0), ntiles and
+# cursor: one int32 device word each.
+def tile_gather_batched(vol, shape, tile, starts, ntiles, cursor, batch, dst, preprocess=None):
+    """slot i < batch of dst ([cols][deps][rows] float32) = the tile of table entry *cursor * batch + i out of vol ([Z][X][Y])"""
+    X, Y, Z = shape
+    deps, rows, cols = tile
+    assert vol.dtype == torch.float32 and vol.is_contiguous() and vol.numel() == X * Y * Z
+    assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.numel() >= batch * deps * rows * cols
+    assert starts.numel() % 3 == 0
+    lo, hi, mean = (float(v) for v in preprocess) if preprocess is not None else (0.0, 0.0, 0.0)
+    check(_l.get().hdu_tile_gather_batched(_vp(vol), X, Y, Z, deps, rows, cols, _i32p(starts), starts.numel() // 3, _i32p(ntiles),
+                                           _i32p(cursor), batch, 0 if preprocess is None else 1, lo, hi, mean, _vp(dst),
+                                           stream()), "hdu_tile_gather_batched")
+
+
+def tile_accumulate(logits, shape, tile, num, starts, ntiles, cursor, batch, slot, score):
+    """score ([Z][X][Y][num]) += softmax of slot `slot` of the step's logits, if that slot is valid"""
+    X, Y, Z = shape
+    deps, rows, cols = tile
+    assert logits.M >= max(1, batch) * deps * rows * cols
+    assert score.dtype == torch.float32 and score.is_contiguous() and score.numel() == X * Y * Z * max(1, min(num, 3))
+    assert starts.numel() % 3 == 0
+    check(_l.get().hdu_tile_accumulate(logits.dtype, logits.ptr, logits.ld, X, Y, Z, deps, rows, cols, num, _i32p(starts),
+                                       starts.numel() // 3, _i32p(ntiles), _i32p(cursor), batch, slot, _vp(score), stream()),
+          "hdu_tile_accumulate")
+
+
+def tile_finalize(score, shape, num, channel, cx, cy, cz, thres=0.5, out_score=None, out_mask=None):
+    """out_score (float32) / out_mask (uint8), [X][Y][Z] = score[z][x][y][channel] / (cx[x] * cy[y] * cz[z]) / its threshold"""
+    X, Y, Z = shape
+    assert score.dtype == torch.float32 and score.is_contiguous() and score.numel() == X * Y * Z * max(1, min(num, 3))
+    for c, n in ((cx, X), (cy, Y), (cz, Z)):
+        assert c.dtype == torch.float32 and c.is_contiguous() and c.numel() == n
+    assert out_score is None or (out_score.dtype == torch.float32 and out_score.numel() == X * Y * Z)
+    assert out_mask is None or (out_mask.dtype == torch.uint8 and out_mask.numel() == X * Y * Z)
+    check(_l.get().hdu_tile_finalize(_vp(score), X, Y, Z, num, channel, _vp(cx), _vp(cy), _vp(cz), float(thres),
+                                     None if out_score is None else _vp(out_score), None if out_mask is None else _vp(out_mask),
+                                     stream()), "hdu_tile_finalize")

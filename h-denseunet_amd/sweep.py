@@ -156,3 +156,165 @@ def plan_for(model, z, num, preprocess=None):
         plan = SweepPlan(model, z, num, preprocess)
         model._sweep_plan = plan
     return plan
+
+
+# ------------------------------------------------------------------ tiled 3-D sweep (lib/funcs.py:54-129 predict_window_mulgpu)
+# The volume is tiled in all three axes with overlapping tiles and the scores are averaged.  The step
+#
+#     hdu_tile_gather_batched -> forward over `batch` tiles -> `batch` x hdu_tile_accumulate -> hdu_sweep_advance
+#
+# reads its tile starts from a device table of (x0, y0, z0) rows, so it is one launch list for every step.
+def tile_starts(n, t):
+    """the tile starts of one axis of length n with tile t (lib/funcs.py:56-58, :74-96): stride (t // 3) * 2, the starts past
+    n - t clamped onto it"""
+    n, t = int(n), int(t)
+    w = (t // 3) * 2
+    if t < 3 or n < t:
+        raise ValueError("a tile of at least 3 and a volume of at least one tile per axis are required")
+    return [min(s, n - t) for s in range(0, n - t + w, w)]
+
+
+def tile_table(shape, tile):
+    """the (x0, y0, z0) of every tile in the reference's order (x outermost, z innermost), int32 [ntiles][3]"""
+    xs, ys, zs = (tile_starts(n, t) for n, t in zip(shape, tile))
+    return np.array([(a, b, c) for a in xs for b in ys for c in zs], np.int32).reshape(-1, 3)
+
+
+def tile_coverage(shape, tile):
+    """(cx, cy, cz) float32: how many tile starts of each axis cover a position.  The tiles are a Cartesian product and every
+    tile is run, so cx[x] * cy[y] * cz[z] tiles cover voxel (x, y, z)."""
+    out = []
+    for n, t in zip(shape, tile):
+        c = np.zeros(int(n), np.float32)
+        for s in tile_starts(n, t):
+            c[s:s + int(t)] += 1
+        out.append(c)
+    return tuple(out)
+
+
+def _check_tiled_model(model, num):
+    if model.kind != "hybrid" or model.ctx.shard_world() > 1:
+        raise ValueError("the tiled sweep drives the unsharded hybrid nets")
+    if not 1 <= num <= 3:
+        raise ValueError("num: 1..3 of the 3 class scores")
+
+
+def _check_preprocess(preprocess):
+    if preprocess is None:
+        return None
+    preprocess = tuple(float(v) for v in preprocess)
+    if len(preprocess) != 3 or not preprocess[0] <= preprocess[1]:
+        raise ValueError("preprocess: (lo, hi, mean) with lo <= hi")
+    return preprocess
+
+
+class TiledSweepPlan:
+    """Resident volume, score, start table, cursor, tile count and coverage vectors of the tiled sweeps of `model` over
+    volumes of `shape`, and the tile step.  graph=True captures the step once and replays it per step (the step runs eagerly
+    on the emulator build); graph=False drives every step from the host with the cursor set by the host -- the same launches."""
+
+    def __init__(self, model, shape, num, preprocess=None):
+        _check_tiled_model(model, num)
+        self.batch, self.deps, self.rows, self.cols, _ = model.input_shape       # batch = the model's window_batch
+        self.shape = tuple(int(v) for v in shape)
+        self.tile = (self.deps, self.rows, self.cols)
+        if len(self.shape) != 3 or any(n < t for n, t in zip(self.shape, self.tile)) or min(self.tile) < 3:
+            raise ValueError("volume smaller than the network window")
+        if not 1 <= self.batch <= ops.SWEEP_MAX_BATCH:
+            raise ValueError("window_batch: 1..%d" % ops.SWEEP_MAX_BATCH)
+        self.preprocess = _check_preprocess(preprocess)
+        self.model, self.num = model, int(num)
+        X, Y, Z = self.shape
+        dev = model.ctx.dev
+        table = tile_table(self.shape, self.tile)
+        self.ntiles = len(table)
+        self.steps = -(-self.ntiles // self.batch)
+        padded = np.repeat(table[-1:], self.steps * self.batch, axis=0)          # whole steps, padded with the last tile
+        padded[:self.ntiles] = table
+        self.table = table
+        self.vol = torch.zeros(Z * X * Y, dtype=torch.float32, device=dev)
+        self.score = torch.zeros((Z, X, Y, self.num), dtype=torch.float32, device=dev)
+        self.starts = torch.from_numpy(np.ascontiguousarray(padded).reshape(-1)).to(dev)
+        self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)              # step index
+        self.ntiles_dev = torch.full((1,), self.ntiles, dtype=torch.int32, device=dev)
+        self.coverage = tuple(torch.from_numpy(c).to(dev) for c in tile_coverage(self.shape, self.tile))
+        self.graph = None
+        self._graph_key = None
+        self.captures = 0        # graph captures so far
+        self.replays = 0         # steps (graph replays, or eager steps) of the last sweep
+
+    def key(self):
+        return (self.shape, self.num, self.preprocess)
+
+    def _step(self):
+        m = self.model
+        ops.tile_gather_batched(self.vol, self.shape, self.tile, self.starts, self.ntiles_dev, self.cursor, self.batch, m.vol,
+                                self.preprocess)
+        m.ctx.run_forward()
+        flat = self.score.reshape(-1)
+        for slot in range(self.batch):
+            ops.tile_accumulate(m.logits.act, self.shape, self.tile, self.num, self.starts, self.ntiles_dev, self.cursor,
+                                self.batch, slot, flat)
+        ops.sweep_advance(self.cursor, self.steps)
+
+    def _capture(self):
+        """one eager warm-up step on a side stream, then the step into a linear graph (as SweepPlan._capture)"""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self._step()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        from .keras_api import _graph_capture
+        with _graph_capture(g):
+            self._step()
+        self.graph = g
+        self._graph_key = self.model._predict_state()
+        self.captures += 1
+
+    def prepare(self):
+        """weights and inference-mode BN coefficients of this sweep, once (learning_phase must be 0)"""
+        ctx = self.model.ctx
+        ctx.prep_weights()
+        ctx.prefold()
+
+    def sweep(self, imgs_test, graph=True):
+        """-> (score float32 device tensor [Z][X][Y][num] of summed softmax scores, (cx, cy, cz) device coverage vectors): the
+        plan's own buffers, valid until the next sweep of this plan"""
+        if tuple(int(v) for v in np.shape(imgs_test)[:3]) != self.shape:
+            raise ValueError("this plan sweeps volumes of shape %s" % (self.shape,))
+        vol = np.ascontiguousarray(np.asarray(imgs_test, np.float32).reshape(self.shape).transpose(2, 0, 1))
+        self.vol.copy_(torch.from_numpy(vol).reshape(-1))
+        ctx = self.model.ctx
+        use_graph = graph and not _l.is_emulator()
+        ctx.learning_phase = 0
+        try:
+            self.prepare()
+            if use_graph and (self.graph is None or self._graph_key != self.model._predict_state()):
+                self._capture()              # (its warm-up step dirties the score and the cursor: they are reset below)
+            self.score.zero_()
+            self.cursor.zero_()
+            self.replays = 0
+            for step in range(self.steps):
+                if use_graph:
+                    self.graph.replay()
+                else:
+                    if not graph:
+                        self.cursor.fill_(step)      # host-driven: the advance launch below computes the same word
+                    self._step()
+                self.replays += 1
+        finally:
+            ctx.end_prefold()
+            ctx.learning_phase = 1
+        return self.score, self.coverage
+
+
+def tiled_plan_for(model, shape, num, preprocess=None):
+    """the model's tiled plan for this volume shape (one plan is kept per model, keyed by shape, `num` and preprocessing)"""
+    plan = getattr(model, "_tiled_sweep_plan", None)
+    key = (tuple(int(v) for v in shape), int(num), _check_preprocess(preprocess))
+    if plan is None or plan.key() != key:
+        plan = TiledSweepPlan(model, shape, num, preprocess)
+        model._tiled_sweep_plan = plan
+    return plan

@@ -47,7 +47,7 @@ const char* hdu_backend(void);
  * DMA path, hdu_wgrad_plan_shape / min_steps), 6 = round 6 (hdu_bn_bwd_apply_sums, bnb_relu bit 2), 7 = round 6 (hdu_split3_*), 8 = hdu_pp_* (device post-processing),
  * 10 = hdu_bn_bwd_fused_pw, hdu_colsum_fold_batched, column-sum table arguments of hdu_bn_bwd_fused / hdu_bn_bwd_apply_sums,
  * 12 = y_ds / ldy_ds / ds_accumulate / ds_only (the up-sampling gradient in the halo-wide data-gradient epilogue). */
-#define HDU_ABI_VERSION 12
+#define HDU_ABI_VERSION 13
 int hdu_abi_version(void);
 size_t hdu_sizeof_conv_desc(void);
 /* Launch profiler (measurement only; replaces nothing in the reference -- Keras has `verbose`, the reference was profiled with
@@ -593,6 +593,40 @@ int hdu_sweep_gather_batched(const float* vol, int z, int64_t plane, int win_pla
 int hdu_sweep_accumulate_batched(int dtype, const void* logits, int64_t ldl, int64_t plane, int win_planes, int z, int num,
                                  const int32_t* starts, int ntable, const int32_t* nwin_dev, const int32_t* cursor, int batch,
                                  float* score, float* count, void* stream);
+
+/* Tiled 3-D sliding-window inference (lib/funcs.py:54-129 predict_window_mulgpu; h-denseunet_amd/sweep.py TiledSweepPlan): the
+ * volume is tiled in all three axes with overlapping tiles of deps x rows x cols voxels and the softmax scores are averaged.
+ * Layouts: resident volume float32 [Z][X][Y] (depth-major), model input float32 [batch][cols][deps][rows], logits
+ * [batch*cols*deps*rows][ldl] in the compute dtype, score float32 [Z][X][Y][num].  The tile position lives in device memory:
+ * starts int32 [ntable][3] = one (x0, y0, z0) per tile, cursor = one int32 word (the step index), ntiles_dev = one int32 word.
+ * Slot i of step *cursor is entry *cursor*batch + i, clamped to the table; each start is clamped to
+ * [0, X-deps] x [0, Y-rows] x [0, Z-cols]; slot i is VALID iff *cursor*batch + i < min(*ntiles_dev, ntable).
+ * hdu_tile_gather_batched: one launch for the `batch` slots: dst[i][k][d][r] = vol[z0+k][x0+d][y0+r], with the optional
+ *   preprocessing of hdu_sweep_gather (preprocess == 0 is a bit-exact copy).  16-byte stores with a scalar head and tail per
+ *   slot; 16-byte loads where a four-float group lies in one source row at an aligned address, scalar loads otherwise.  Slots
+ *   that are not valid still gather their clamped entry, so the forward always runs on finite data: ntiles_dev is therefore
+ *   NOT read by the gather (it is checked like the other pointers and keeps the argument list of hdu_sweep_gather_batched, so
+ *   that one set of plan buffers is handed to every launch of the step).
+ * hdu_tile_accumulate: ONE slot: score[z0+k][x0+d][y0+r][0..num) += p, p = what hdu_softmax_accumulate (the very expression)
+ *   leaves on a zeroed buffer for the voxel's logits: the softmax is rounded to float32 before it is added, as the reference
+ *   adds a float32 softmax array.  A launch whose slot is not valid writes nothing.  The tiles of a step overlap, so the caller
+ *   issues the slots as `batch` launches in slot order: stream order makes the float sequence of `+=` per voxel the
+ *   reference's tile order, without atomics.
+ * hdu_sweep_advance serves unchanged, with the number of steps as its bound.
+ * hdu_tile_finalize: cx [X], cy [Y], cz [Z] float32 = how many tile starts of each axis cover a position; the tiles are a
+ *   Cartesian product, so cx[x]*cy[y]*cz[z] tiles covered voxel (x, y, z).  s = score[z][x][y][channel] / (cx[x]*cy[y]*cz[z]),
+ *   one float32 IEEE division (0 / 0 = NaN where nothing covered).  out_score float32 [X][Y][Z] = s and out_mask uint8
+ *   [X][Y][Z] = ((double)s >= thres), the raster order of the hdu_pp_* kernels; either may be NULL, not both.
+ * Tile dims >= 3 and <= the volume's, 1 <= batch <= HDU_SWEEP_MAX_BATCH, 0 <= slot < batch, num in 1..3, channel < num,
+ * ldl >= 3, volumes below 2^32 - 1 voxels; a bad argument returns HDU_ERR_ARG and launches nothing. */
+int hdu_tile_gather_batched(const float* vol, int X, int Y, int Z, int deps, int rows, int cols, const int32_t* starts, int ntable,
+                            const int32_t* ntiles_dev, const int32_t* cursor, int batch, int preprocess, float lo, float hi,
+                            float mean, float* dst, void* stream);
+int hdu_tile_accumulate(int dtype, const void* logits, int64_t ldl, int X, int Y, int Z, int deps, int rows, int cols, int num,
+                        const int32_t* starts, int ntable, const int32_t* ntiles_dev, const int32_t* cursor, int batch, int slot,
+                        float* score, void* stream);
+int hdu_tile_finalize(const float* score, int X, int Y, int Z, int num, int channel, const float* cx, const float* cy,
+                      const float* cz, double thres, float* out_score, uint8_t* out_mask, void* stream);
 
 /* ------------------------------------------------------------------ per-step re-initialisation
  * The accumulators a training step adds into (epilogue statistics, fused BN-backward slot rows, the flat gradient buffer the
