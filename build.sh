@@ -7,7 +7,7 @@ set -e
 cd "$(dirname "$0")"
 SRC=h-denseunet_amd/csrc
 what=${1:-all}
-UNITS="conv_igemm.hip conv_halo_wide.hip rowops.hip augment.hip postproc.hip hdu_core.cpp hdu_comm.cpp"
+UNITS="conv_igemm.hip conv_halo_wide.hip rowops.hip augment.hip postproc.hip metrics.hip hdu_core.cpp hdu_comm.cpp"
 HDRS="$SRC/*.h include/hdu.h tests/hipemu/hipemu.h build.sh"
 mkdir -p build/hip build/emu
 

@@ -422,7 +422,11 @@ __device__ __forceinline__ unsigned long long hdu_atomic_max_u64(unsigned long l
   return old;
 }
 __device__ __forceinline__ unsigned hdu_load_relaxed_u32(const unsigned* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+__device__ __forceinline__ unsigned long long hdu_atomic_add_u64(unsigned long long* p, unsigned long long v) {
+  return __atomic_fetch_add(p, v, __ATOMIC_RELAXED);
+}
 #else
+__device__ __forceinline__ unsigned long long hdu_atomic_add_u64(unsigned long long* p, unsigned long long v) { return atomicAdd(p, v); }
 __device__ __forceinline__ unsigned hdu_atomic_min_u32(unsigned* p, unsigned v) { return atomicMin(p, v); }
 __device__ __forceinline__ unsigned hdu_atomic_max_u32(unsigned* p, unsigned v) { return atomicMax(p, v); }
 __device__ __forceinline__ unsigned long long hdu_atomic_max_u64(unsigned long long* p, unsigned long long v) { return atomicMax(p, v); }

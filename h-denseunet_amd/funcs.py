@@ -213,6 +213,11 @@ def segment_liver_tumor_device(score, count, shape, mask_dev, thres_liver=0.5, t
     [z][deps][rows][num], count the windows per plane ([z], host or device), shape = (x, y, z) of the CT volume, mask_dev
     the dilated coarse liver mask of liver_window_from_mask_device.  Returns the uint8 label volume (x, y, z)."""
     shape = tuple(int(v) for v in shape)
+    return _segment_liver_tumor_labels(score, count, shape, mask_dev, thres_liver, thres_tumor).cpu().numpy().reshape(shape)
+
+
+def _segment_liver_tumor_labels(score, count, shape, mask_dev, thres_liver, thres_tumor):
+    """segment_liver_tumor_device up to the download: the flat uint8 label volume, still on the device"""
     ws = _PostWorkspace(shape, score.device)
     if mask_dev.dtype != torch.uint8 or mask_dev.numel() != ws.n or mask_dev.device != score.device:
         raise ValueError("mask_dev: the uint8 device mask of liver_window_from_mask_device for this volume")
@@ -234,7 +239,7 @@ def segment_liver_tumor_device(score, count, shape, mask_dev, thres_liver=0.5, t
     counts = torch.cat([n_liver, n_mask]).cpu().numpy()
     if counts[0] == 0 or counts[1] == 0:
         raise ValueError(_NO_COMPONENT)
-    return a.cpu().numpy().reshape(shape)
+    return a
 
 
 def segment_volume(model, imgs_test, liver_mask, args, thres_liver=0.5, thres_tumor=0.9, mode="eager", preprocess=None):
@@ -248,6 +253,23 @@ def segment_volume(model, imgs_test, liver_mask, args, thres_liver=0.5, thres_tu
     mask_dev, mini, maxi = liver_window_from_mask_device(liver_mask)
     score, score_num = sweep_scores(model, imgs_test, 3, mini, maxi, args, mode=mode, preprocess=preprocess)
     return segment_liver_tumor_device(score, score_num, shape, mask_dev, thres_liver, thres_tumor)
+
+
+def evaluate_volume(model, imgs_test, liver_mask, truth, args, spacing=None, thres_liver=0.5, thres_tumor=0.9, mode="eager",
+                    preprocess=None):
+    """segment_volume followed by metrics.evaluate_labels_device against the label volume `truth`, the predicted labels
+    staying in HBM in between: returns (uint8 label volume (x, y, z), {"liver": {...}, "tumor": {...}}) -- what
+    metrics.evaluate_labels(segment_volume(...), truth, spacing) computes on the host.
+    `spacing`: None or the voxel size in mm along x, y, z; the other arguments are segment_volume's."""
+    from . import metrics
+    shape = tuple(int(v) for v in np.shape(imgs_test)[:3])
+    if tuple(np.shape(liver_mask)) != shape or tuple(np.shape(truth)) != shape:
+        raise ValueError("liver_mask and truth must have the shape of the CT volume")
+    mask_dev, mini, maxi = liver_window_from_mask_device(liver_mask)
+    score, score_num = sweep_scores(model, imgs_test, 3, mini, maxi, args, mode=mode, preprocess=preprocess)
+    labels = _segment_liver_tumor_labels(score, score_num, shape, mask_dev, thres_liver, thres_tumor)
+    evaluation = metrics.evaluate_labels_device(labels, truth, spacing, shape=shape)
+    return labels.cpu().numpy().reshape(shape), evaluation
 
 
 # ------------------------------------------------------------------ tiled 3-D sliding-window inference (lib/funcs.py:54-153)

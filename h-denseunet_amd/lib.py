@@ -207,6 +207,10 @@ _SIGS = {
     "hdu_pp_fill_holes": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
     "hdu_pp_bbox": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p]),
     "hdu_pp_merge": (c_int, [c_int, c_p, c_p, c_i64, c_p, c_p]),
+    "hdu_metric_counts": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p]),
+    "hdu_metric_border": (c_int, [c_p, c_int, c_int, c_int, c_int, c_p, c_p]),
+    "hdu_metric_edt": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
+    "hdu_metric_sample": (c_int, [c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p]),
     "hdu_zero_regions": (c_int, [c_p, c_int, c_u32, c_p, c_u32, c_p]),
     "hdu_zero": (c_int, [c_p, ctypes.c_uint64, c_p]),
     "hdu_split3_entry_fill": (c_int, [c_p, c_p, c_i64, c_i64, c_int, c_p, c_p, c_int, c_int, c_p, c_u32, ctypes.POINTER(c_u32)]),
@@ -232,7 +236,7 @@ class HduError(RuntimeError):
     pass
 
 
-ABI_VERSION = 13       # include/hdu.h HDU_ABI_VERSION
+ABI_VERSION = 14       # include/hdu.h HDU_ABI_VERSION
 
 
 def product_library_path():

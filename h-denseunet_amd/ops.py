@@ -770,6 +770,35 @@ def pp_merge(op, a, b, out):
     check(_l.get().hdu_pp_merge(op, _vp(a), _vp(b), out.numel(), _vp(out), stream()), "hdu_pp_merge")
 
 
+# ------------------------------------------------------------------ segmentation metrics (include/hdu.h: hdu_metric_*)
+# The volumes of hdu_pp_*; float64 tensors for the distance field and the partials, int64 storage for the 64-bit result words.
+METRIC_LIVER, METRIC_TUMOR = 0, 1     # class_mode: label >= 1 (a plain mask: nonzero) / label == 2
+METRIC_PARTIALS = 1024                # include/hdu.h HDU_METRIC_PARTIALS
+
+
+def metric_counts(pred, truth, shape, class_mode, counts):
+    """counts: int64 [3], zeroed; += |R|, |T|, |R & T|"""
+    assert counts.dtype == torch.int64 and counts.numel() >= 3
+    check(_l.get().hdu_metric_counts(_vp(pred), _vp(truth), *shape, class_mode, _vp(counts), stream()), "hdu_metric_counts")
+
+
+def metric_border(src, shape, class_mode, out):
+    check(_l.get().hdu_metric_border(_vp(src), *shape, class_mode, _vp(out), stream()), "hdu_metric_border")
+
+
+def metric_edt(feature, shape, sampling, tmp, d2):
+    """d2 (float64) = squared distance to the nearest set voxel of `feature`; sampling: None or three floats (x, y, z)"""
+    assert tmp.dtype == torch.float64 and d2.dtype == torch.float64
+    s = None if sampling is None else (ctypes.c_double * 3)(*[float(v) for v in sampling])
+    check(_l.get().hdu_metric_edt(_vp(feature), *shape, s, _vp(tmp), _vp(d2), stream()), "hdu_metric_edt")
+
+
+def metric_sample(sample, d2, shape, partial, out):
+    """partial: float64 [4 * METRIC_PARTIALS]; out: int64 [4] = n, then the float64 bits of sum sqrt(d2), sum d2, max d2"""
+    assert partial.dtype == torch.float64 and partial.numel() >= 4 * METRIC_PARTIALS and out.dtype == torch.int64
+    check(_l.get().hdu_metric_sample(_vp(sample), _vp(d2), *shape, _vp(partial), _vp(out), stream()), "hdu_metric_sample")
+
+
 # ------------------------------------------------------------------ table-driven window step (include/hdu.h: hdu_sweep_*)
 # starts: int32 device table of window start planes, cursor: one int32 device word; every launch reads c0 = starts[*cursor].
 def _i32p(t):

@@ -46,8 +46,9 @@ const char* hdu_backend(void);
  * 4 = round 3 (hdu_zero_regions, hdu_comm_*), 5 = round 4 (hdu_profile_*, pointwise convs with a fused BN prologue on the
  * DMA path, hdu_wgrad_plan_shape / min_steps), 6 = round 6 (hdu_bn_bwd_apply_sums, bnb_relu bit 2), 7 = round 6 (hdu_split3_*), 8 = hdu_pp_* (device post-processing),
  * 10 = hdu_bn_bwd_fused_pw, hdu_colsum_fold_batched, column-sum table arguments of hdu_bn_bwd_fused / hdu_bn_bwd_apply_sums,
- * 12 = y_ds / ldy_ds / ds_accumulate / ds_only (the up-sampling gradient in the halo-wide data-gradient epilogue). */
-#define HDU_ABI_VERSION 13
+ * 12 = y_ds / ldy_ds / ds_accumulate / ds_only (the up-sampling gradient in the halo-wide data-gradient epilogue),
+ * 14 = hdu_metric_* (device-resident segmentation metrics). */
+#define HDU_ABI_VERSION 14
 int hdu_abi_version(void);
 size_t hdu_sizeof_conv_desc(void);
 /* Launch profiler (measurement only; replaces nothing in the reference -- Keras has `verbose`, the reference was profiled with
@@ -718,6 +719,33 @@ int hdu_pp_largest(const uint32_t* root, int X, int Y, int Z, uint32_t* area, ui
 int hdu_pp_fill_holes(const uint8_t* mask, int X, int Y, int Z, uint32_t* root, uint8_t* flag, uint8_t* out, void* stream);
 int hdu_pp_bbox(const uint8_t* mask, int X, int Y, int Z, uint32_t* box, void* stream);
 int hdu_pp_merge(int op, const uint8_t* a, const uint8_t* b, int64_t n, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------ segmentation metrics of a label volume
+ * Device-resident form of h-denseunet_amd/metrics.py (MedPy's metric.binary: overlap counts, surface distances with
+ * connectivity 1).  Conventions of hdu_pp_*: flat uint8 volumes in raster order [X][Y][Z] (z fastest), asynchronous on the
+ * caller's stream, caller-owned workspace, volumes of 2^32 - 1 voxels or more refused (HDU_ERR_ARG).
+ * class_mode selects the structure of a label volume {0, 1, 2}: HDU_METRIC_LIVER = label >= 1 (a plain mask: nonzero),
+ * HDU_METRIC_TUMOR = label == 2.
+ *
+ * hdu_metric_counts: counts[0..2] += |R|, |T|, |R & T| of pred / truth under class_mode; three ZEROED 64-bit words.  Integer
+ *   atomics, one per workgroup: exact whatever the order.
+ * hdu_metric_border: out = set && (a 6-neighbour is clear or lies outside the volume) = mask ^ binary_erosion(mask) with
+ *   border_value 0; out must not alias in.
+ * hdu_metric_edt: d2 = squared Euclidean distance of every voxel to the nearest set voxel of `feature`, float64, +inf
+ *   everywhere when no voxel is set.  sampling: three positive doubles (x, y, z) on the HOST, read during the call; NULL =
+ *   unit voxels.  Three separable passes in the fixed order z, y, x; every minimum is the exact minimum of
+ *   g[q] + ((p - q) * s)^2 evaluated in double, so unit spacing gives the exact integers.  tmp: X*Y*Z doubles of workspace.
+ *   Lines of any length up to 2^30 voxels per axis.
+ * hdu_metric_sample: over the set voxels of `sample`: out[0] = n (uint64), out[1] = sum sqrt(d2), out[2] = sum d2,
+ *   out[3] = max d2 (float64 in the 64-bit words; 0 for an empty sample).  Bit-repeatable: per-workgroup partials in workgroup
+ *   order (partial: 4 * HDU_METRIC_PARTIALS doubles), then one workgroup in a fixed order; no floating-point atomics. */
+#define HDU_METRIC_LIVER 0
+#define HDU_METRIC_TUMOR 1
+#define HDU_METRIC_PARTIALS 1024
+int hdu_metric_counts(const uint8_t* pred, const uint8_t* truth, int X, int Y, int Z, int class_mode, uint64_t* counts, void* stream);
+int hdu_metric_border(const uint8_t* in, int X, int Y, int Z, int class_mode, uint8_t* out, void* stream);
+int hdu_metric_edt(const uint8_t* feature, int X, int Y, int Z, const double* sampling, double* tmp, double* d2, void* stream);
+int hdu_metric_sample(const uint8_t* sample, const double* d2, int X, int Y, int Z, double* partial, uint64_t* out, void* stream);
 
 /* ------------------------------------------------------------------ collectives (RCCL over xGMI)
  * The reference's only multi-GPU mechanism is in-graph tower replication (K.utils2/multi_gpu.py:7-69: the gradient sum is
