@@ -279,6 +279,52 @@ __global__ __launch_bounds__(256) void pp_merge_kernel(int op, const uint8_t* __
   }
 }
 
+// ------------------------------------------------------------------ label planes of the 2-D slice sweep -> raster order
+// labels uint8 [Z][H][W] (the argmax planes of hdu_slice_argmax_store) -> out uint8 [X][Y][Z], zero outside the H x W window.
+// For one x this is a byte transpose [Z][W] -> [W][Z].  One workgroup = one x, a 64 (z) x 64 (y) tile held in LDS as
+// tile[y][z / 4]: one 32-bit word = the bytes of four consecutive z, the unit the raster order stores.
+//   read phase:  a wave holds one z-quad and 64 consecutive y: four byte loads per lane, each a 64-byte run along y, packed into
+//                ONE ds_write_b32 at word 17 * y + zq.  The row pitch of 17 words is odd, so the 32 lanes of a half-wave
+//                (consecutive y) fall on 32 different banks.
+//   write phase: 16 lanes = the 16 z-quads of one y: one 64-byte run along z per y.  The four y of a wave are 16 rows apart:
+//                a half-wave reads the words 17 * y + 0..15 and 17 * (y + 16) + 0..15 = 17 * y + 16 + 0..15 (mod 32), again 32
+//                different banks.  The word is stored whole where it is aligned and inside Z, byte by byte otherwise.
+#define PP_RASTER_PITCH 17
+__global__ __launch_bounds__(256) void slice_labels_to_raster_kernel(const uint8_t* __restrict__ labels, int Y, int Z, int H, int W,
+                                                                     uint8_t* __restrict__ out) {
+  __shared__ unsigned tile[64 * PP_RASTER_PITCH];
+  const int x = blockIdx.x, y0 = blockIdx.y * 64, z0 = blockIdx.z * 64;
+  const int tid = threadIdx.x;
+  for (int k = 0; k < 4; ++k) {
+    const int e = k * 256 + tid, zq = e >> 6, yl = e & 63;
+    const int y = y0 + yl;
+    unsigned word = 0;
+    if (x < H && y < W) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int z = z0 + 4 * zq + j;
+        if (z < Z) word |= (unsigned)labels[((size_t)z * H + x) * W + y] << (8 * j);
+      }
+    }
+    tile[yl * PP_RASTER_PITCH + zq] = word;
+  }
+  __syncthreads();
+  for (int k = 0; k < 4; ++k) {
+    const int zq = tid & 15, yl = k * 4 + (tid >> 6) + 16 * ((tid >> 4) & 3);
+    const int y = y0 + yl, z = z0 + 4 * zq;
+    if (y >= Y || z >= Z) continue;
+    const unsigned word = tile[yl * PP_RASTER_PITCH + zq];
+    uint8_t* __restrict__ o = out + ((size_t)x * Y + y) * Z + z;
+    if (z + 3 < Z && ((uintptr_t)o & 3u) == 0) {
+      *(unsigned*)o = word;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (z + j < Z) o[j] = (uint8_t)(word >> (8 * j));
+    }
+  }
+}
+
 // ------------------------------------------------------------------ C-ABI (include/hdu.h)
 #define PP_LAUNCH(kern, n, ...) HDU_LAUNCH(kern, dim3(hdu_grid_1d((n), 256, 8192)), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__)
 
@@ -366,4 +412,16 @@ extern "C" int hdu_pp_merge(int op, const uint8_t* a, const uint8_t* b, int64_t 
   if (n == 0) return 0;
   PP_LAUNCH(pp_merge_kernel, n, op, a, b, (long long)n, out);
   return hdu_check_launch("pp_merge");
+}
+
+extern "C" int hdu_slice_labels_to_raster(const uint8_t* labels, int X, int Y, int Z, int H, int W, uint8_t* out, void* stream) {
+  long long N;
+  if (int e = pp_check_dims(X, Y, Z, "slice_labels_to_raster: bad volume dims", &N)) return e;
+  if (!labels || !out || labels == out) return hdu_set_error(HDU_ERR_ARG, "slice_labels_to_raster: bad args (in-place not supported)");
+  if (H < 1 || W < 1 || H > X || W > Y) return hdu_set_error(HDU_ERR_ARG, "slice_labels_to_raster: bad args (1 <= H <= X, 1 <= W <= Y)");
+  if ((Z + 63) / 64 > 65535 || (Y + 63) / 64 > 65535)
+    return hdu_set_error(HDU_ERR_ARG, "slice_labels_to_raster: bad args (Y and Z below 64 * 65536)");
+  HDU_LAUNCH(slice_labels_to_raster_kernel, dim3(X, (Y + 63) / 64, (Z + 63) / 64), dim3(256), 0, (hipStream_t)stream, labels, Y, Z,
+             H, W, out);
+  return hdu_check_launch("slice_labels_to_raster");
 }

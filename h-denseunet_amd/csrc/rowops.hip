@@ -2462,6 +2462,80 @@ __global__ __launch_bounds__(256) void tile_finalize_kernel(const float* __restr
   }
 }
 
+// ------------------------------------------------------------------ 2-D slice sweep step (include/hdu.h: hdu_slice_*)
+// train_2ddense.py:58-61 feeds the planes c-1, c, c+1 as the three channels of a 2-D input.  Step *cursor (clamped to the
+// nsteps = ceil(Z / batch) steps) holds the centre planes *cursor * batch + i; a slot past the volume repeats plane Z-1.
+__device__ __forceinline__ long long slice_step_first(const int* __restrict__ cursor, int Z, int batch) {
+  const int nsteps = (Z + batch - 1) / batch;
+  int s = *cursor;
+  s = s < 0 ? 0 : (s >= nsteps ? nsteps - 1 : s);
+  return (long long)s * batch;
+}
+
+// element j = (h * W + w) * 3 + k of a slot with centre plane c -> its offset in the resident volume [Z][X][Y]; the planes
+// before the first and after the last are the first and the last (include/hdu.h: the end planes are replicated)
+__device__ __forceinline__ long long slice_src_offset(long long j, int c, int X, int Y, int Z, int W) {
+  const int k = (int)(j % 3);
+  const long long hw = j / 3;
+  const int w = (int)(hw % W);
+  const long long h = hw / W;
+  int zc = c + k - 1;
+  zc = zc < 0 ? 0 : (zc > Z - 1 ? Z - 1 : zc);
+  return ((long long)zc * X + h) * Y + w;
+}
+
+// slot blockIdx.y: dst[slot][h][w][k] = pre(vol[c+k-1][h][w]).  The slot is contiguous (16-byte stores between a scalar head
+// and tail); the four floats of a store come from up to three planes, so they are four scalar loads, and the lanes of a wave
+// walk along y within each plane.
+__global__ __launch_bounds__(256) void slice_gather_batched_kernel(const float* __restrict__ vol, int X, int Y, int Z, int H, int W,
+                                                                   const int* __restrict__ cursor, int batch, int pre, float lo,
+                                                                   float hi, float mean, float* __restrict__ dst0) {
+  const int slot = blockIdx.y;
+  const long long entry = slice_step_first(cursor, Z, batch) + slot;
+  const int c = entry > Z - 1 ? Z - 1 : (int)entry;
+  const long long n = (long long)H * W * 3;
+  float* __restrict__ dst = dst0 + slot * n;
+  long long head = (long long)(((16u - (unsigned)((uintptr_t)dst & 15u)) & 15u) >> 2);
+  if (head > n) head = n;
+  const long long n4 = (n - head) >> 2;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    const long long j = head + 4 * i;
+    f32x4 v = f32x4{vol[slice_src_offset(j, c, X, Y, Z, W)], vol[slice_src_offset(j + 1, c, X, Y, Z, W)],
+                    vol[slice_src_offset(j + 2, c, X, Y, Z, W)], vol[slice_src_offset(j + 3, c, X, Y, Z, W)]};
+    if (pre) v = f32x4{sweep_pre(v.x, 1, lo, hi, mean), sweep_pre(v.y, 1, lo, hi, mean), sweep_pre(v.z, 1, lo, hi, mean),
+                       sweep_pre(v.w, 1, lo, hi, mean)};
+    *(f32x4*)(dst + j) = v;
+  }
+  if (blockIdx.x == 0) {
+    for (long long j = threadIdx.x; j < head; j += 256)
+      dst[j] = sweep_pre(vol[slice_src_offset(j, c, X, Y, Z, W)], pre, lo, hi, mean);
+    for (long long j = head + 4 * n4 + threadIdx.x; j < n; j += 256)
+      dst[j] = sweep_pre(vol[slice_src_offset(j, c, X, Y, Z, W)], pre, lo, hi, mean);
+  }
+}
+
+// one thread per (slot, pixel): the index of the largest of the pixel's three logits onto the label plane of the slot's centre
+// plane.  Strict `>` in class order: the first maximum wins, as np.argmax; -0.0 > +0.0 is false either way, so they tie.  A
+// slot past the volume writes nothing.
+template <typename T>
+__global__ __launch_bounds__(256) void slice_argmax_store_kernel(const T* __restrict__ logits, long long ldl, long long plane, int Z,
+                                                                 const int* __restrict__ cursor, int batch,
+                                                                 uint8_t* __restrict__ labels) {
+  const long long first = slice_step_first(cursor, Z, batch);
+  const long long M = (long long)batch * plane;
+  for (long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long long)gridDim.x * blockDim.x) {
+    const long long zz = first + m / plane;
+    if (zz >= Z) continue;
+    const T* __restrict__ lg = logits + m * ldl;
+    const float l0 = Chunk<T>::load1(lg), l1 = Chunk<T>::load1(lg + 1), l2 = Chunk<T>::load1(lg + 2);
+    int best = 0;
+    float top = l0;
+    if (l1 > top) { best = 1; top = l1; }
+    if (l2 > top) best = 2;
+    labels[zz * plane + m % plane] = (uint8_t)best;
+  }
+}
+
 #define HDU_T_LAUNCH(T, kern, n, ...) \
   HDU_LAUNCH((kern<T>), dim3(hdu_grid_1d((n), 256, 4096)), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__)
 #define HDU_CHECK_DTYPE(what) \
@@ -2655,6 +2729,39 @@ extern "C" int hdu_tile_finalize(const float* score, int X, int Y, int Z, int nu
   HDU_LAUNCH(tile_finalize_kernel, dim3(X, (Y + 63) / 64, (Z + 63) / 64), dim3(256), 0, (hipStream_t)stream, score, X, Y, Z, num,
              channel, cx, cy, cz, thres, out_score, out_mask);
   return hdu_check_launch("tile_finalize");
+}
+
+extern "C" int hdu_slice_gather_batched(const float* vol, int X, int Y, int Z, int H, int W, const int32_t* cursor, int batch,
+                                        int preprocess, float lo, float hi, float mean, float* dst, void* stream) {
+  if (!vol || !cursor || !dst) return hdu_set_error(HDU_ERR_ARG, "slice_gather_batched: null pointer");
+  if (Z < 1 || H < 1 || W < 1 || H > X || W > Y || batch < 1 || batch > HDU_SLICE_MAX_BATCH)
+    return hdu_set_error(HDU_ERR_ARG, "slice_gather_batched: bad args (Z >= 1, 1 <= H <= X, 1 <= W <= Y, batch in 1.."
+                                      HDU_STR(HDU_SLICE_MAX_BATCH) ")");
+  if ((long long)X * Y * Z >= 0xFFFFFFFFll)
+    return hdu_set_error(HDU_ERR_ARG, "slice_gather_batched: volumes of 2^32 - 1 voxels or more are not supported");
+  if (((uintptr_t)vol & 3) || ((uintptr_t)dst & 3) || ((uintptr_t)cursor & 3))
+    return hdu_set_error(HDU_ERR_ARG, "slice_gather_batched: float32 / int32 buffers must be 4-byte aligned");
+  if (preprocess && !(lo <= hi)) return hdu_set_error(HDU_ERR_ARG, "slice_gather_batched: preprocessing needs lo <= hi");
+  const long long n = (long long)H * W * 3;
+  HDU_LAUNCH(slice_gather_batched_kernel, dim3(hdu_grid_1d((n + 3) / 4, 256, 4096), batch), dim3(256), 0, (hipStream_t)stream, vol,
+             X, Y, Z, H, W, (const int*)cursor, batch, preprocess ? 1 : 0, lo, hi, mean, dst);
+  return hdu_check_launch("slice_gather_batched");
+}
+
+extern "C" int hdu_slice_argmax_store(int dtype, const void* logits, int64_t ldl, int64_t plane, int Z, const int32_t* cursor,
+                                      int batch, uint8_t* labels, void* stream) {
+  if (!logits || !cursor || !labels) return hdu_set_error(HDU_ERR_ARG, "slice_argmax_store: null pointer");
+  if (ldl < 3 || plane < 1 || Z < 1 || batch < 1 || batch > HDU_SLICE_MAX_BATCH)
+    return hdu_set_error(HDU_ERR_ARG, "slice_argmax_store: bad args (3 classes, plane >= 1, Z >= 1, batch in 1.."
+                                      HDU_STR(HDU_SLICE_MAX_BATCH) ")");
+  if (plane * (long long)Z >= 0xFFFFFFFFll)
+    return hdu_set_error(HDU_ERR_ARG, "slice_argmax_store: volumes of 2^32 - 1 voxels or more are not supported");
+  HDU_CHECK_DTYPE("slice_argmax_store");
+  if ((uintptr_t)cursor & 3) return hdu_set_error(HDU_ERR_ARG, "slice_argmax_store: int32 buffers must be 4-byte aligned");
+  const long long M = (long long)batch * plane;
+  if (dtype == HDU_BF16) { HDU_T_LAUNCH(bf16_t, slice_argmax_store_kernel, M, (const bf16_t*)logits, (long long)ldl, (long long)plane, Z, (const int*)cursor, batch, labels); }
+  else { HDU_T_LAUNCH(float, slice_argmax_store_kernel, M, (const float*)logits, (long long)ldl, (long long)plane, Z, (const int*)cursor, batch, labels); }
+  return hdu_check_launch("slice_argmax_store");
 }
 
 // ------------------------------------------------------------------ per-step re-initialisation (include/hdu.h)

@@ -172,8 +172,19 @@ def liver_window_from_mask_device(mask):
     n = _check_volume(shape)
     dev = ops.device()
     src = torch.from_numpy(np.ascontiguousarray(m != 0).view(np.uint8).reshape(n)).to(dev)
+    return liver_window_from_device_mask(src, shape)
+
+
+def liver_window_from_device_mask(mask_dev, shape):
+    """liver_window_from_mask of a mask that is already on the device: `mask_dev` is a flat uint8 device tensor in raster
+    order (nonzero is the liver), shape = (x, y, z); returns (dilated mask as a flat uint8 device tensor, mini, maxi)"""
+    shape = tuple(int(v) for v in shape)
+    n = _check_volume(shape)
+    if not torch.is_tensor(mask_dev) or mask_dev.dtype != torch.uint8 or mask_dev.numel() != n:
+        raise ValueError("mask_dev: a flat uint8 device mask of this volume")
+    dev = mask_dev.device
     out = torch.empty(n, dtype=torch.uint8, device=dev)
-    ops.pp_dilate(src, shape, out)
+    ops.pp_dilate(mask_dev.contiguous().reshape(n), shape, out)
     box = torch.tensor([-1, -1, -1, 0, 0, 0], dtype=torch.int32, device=dev)
     ops.pp_bbox(out, shape, box)
     b = box.cpu().numpy().view(np.uint32).astype(np.int64)
@@ -374,3 +385,111 @@ def segment_volume_tiled(model, imgs_test, mode="eager", thres=0.5, channel=1, p
         raise ValueError("channel: 0..2")
     score, coverage = tiled_sweep_scores(model, imgs_test, 3, mode=mode, preprocess=preprocess)
     return segment_tiled_scores(score, coverage, shape, thres, channel)
+
+
+# ------------------------------------------------------------------ 2-D slice sweep and the CT cascade (test.py:52-112)
+# test.py:58 loads the coarse liver mask `livermask/<id>-ori.nii` from a file; the network that makes it is the 2-D DenseUNet of
+# train_2ddense.py, which sees the planes c-1, c, c+1 of the volume as the three channels of one slice (:58-61).  Here that net
+# runs over every plane of a volume resident in HBM (sweep.SliceSweepPlan, include/hdu.h: hdu_slice_*) and the argmax labels
+# stay there, so the cascade  raw CT -> coarse liver mask -> liver window -> hybrid sweep -> label volume  needs no host mask.
+def _check_slice_call(model, imgs_test, mode):
+    if mode not in ("eager", "graph"):
+        raise ValueError("mode: 'eager' or 'graph', not %r" % (mode,))
+    if model.kind != "2d" or model.ctx.shard_world() > 1 or getattr(model, "window_batch", 1) != 1:
+        raise ValueError("the slice sweep drives the unsharded 2-D net (no window_batch)")
+    shape = tuple(int(v) for v in np.shape(imgs_test)[:3])
+    _, H, W, _ = model.input_shape
+    if len(shape) != 3 or shape[0] < H or shape[1] < W or shape[2] < 1:
+        raise ValueError("volume smaller than the network window")
+    return shape
+
+
+def slice_sweep_labels(model, imgs_test, mode="eager", preprocess=None):
+    """the 2-D `model` over every plane of the (x, y, z) volume, left on the device: the uint8 labels {0, 1, 2} (argmax of the
+    three logits, first maximum) as a flat device tensor in raster order [x][y][z], zero outside the model's top-left H x W
+    window.  It is the plan's own buffer, valid until the next slice sweep of this model.
+    Plane c is predicted from the planes c-1, c, c+1; the end planes are replicated (include/hdu.h).  `batch` = the model's b
+    planes run per forward; the padding slots of the last step repeat the last plane and store nothing.
+    mode="eager": every step driven from the host, which sets the step cursor.  mode="graph": one captured step replayed
+    ceil(z / b) times.  Both run the same launches.
+    preprocess=(lo, hi, mean): `imgs_test` is raw; the gather writes min(max(v, lo), hi) - mean."""
+    shape = _check_slice_call(model, imgs_test, mode)
+    return sweep.slice_plan_for(model, shape, preprocess).sweep(imgs_test, graph=(mode == "graph"))
+
+
+def segment_volume_2d(model, imgs_test, mode="eager", preprocess=None):
+    """slice_sweep_labels as a host uint8 array (x, y, z): the 2-D DenseUNet as a whole-volume segmenter"""
+    shape = _check_slice_call(model, imgs_test, mode)
+    labels = slice_sweep_labels(model, imgs_test, mode=mode, preprocess=preprocess)
+    return labels.cpu().numpy().reshape(shape).copy()          # (the plan's buffer is reused: never hand out a view of it)
+
+
+def slice_labels_host(model, imgs_test, preprocess=None):
+    """the host composition segment_volume_2d replaces, and its specification: numpy batches of (c-1, c, c+1) slices with the
+    same edge-plane and padding rules, Model.predict, np.argmax; returns the uint8 array (x, y, z)"""
+    shape = _check_slice_call(model, imgs_test, "eager")
+    X, Y, Z = shape
+    N, H, W, _ = model.input_shape
+    vol = np.asarray(imgs_test, np.float32).reshape(shape)[:H, :W, :]
+    if preprocess is not None:
+        lo, hi, mean = (np.float32(v) for v in preprocess)
+        vol = np.clip(vol, lo, hi) - mean
+    out = np.zeros(shape, np.uint8)
+    for s0 in range(0, Z, N):
+        centres = [min(s0 + i, Z - 1) for i in range(N)]
+        x = np.stack([np.stack([vol[:, :, min(max(c + k - 1, 0), Z - 1)] for k in range(3)], axis=-1) for c in centres])
+        lab = np.argmax(model.predict(x), axis=-1).astype(np.uint8)
+        for i in range(min(N, Z - s0)):
+            out[:H, :W, s0 + i] = lab[i]
+    return out
+
+
+def coarse_liver_mask_device(model, imgs_test, mode="eager", preprocess=None, largest=True):
+    """the coarse liver mask test.py:58 reads from `livermask/`, made on the device: labels != 0 of slice_sweep_labels (liver
+    and tumour merged, as liver_window_from_mask merges them), as a flat uint8 device tensor in raster order.  largest=True
+    keeps its largest 26-connected component (ValueError "no foreground component" when there is none)."""
+    shape = _check_slice_call(model, imgs_test, mode)
+    labels = slice_sweep_labels(model, imgs_test, mode=mode, preprocess=preprocess)
+    ws = _PostWorkspace(shape, labels.device)
+    out = ws.mask()
+    if not largest:
+        ops.pp_merge(ops.PP_AND, labels, labels, out)          # out = labels != 0
+        return out
+    ncomp = ws.largest26(labels, out)                          # (nonzero = set: the labels serve as the mask)
+    if int(ncomp.cpu()[0]) == 0:
+        raise ValueError(_NO_COMPONENT)
+    return out
+
+
+def _segment_ct_labels(model2d, model_hybrid, imgs_test, args, thres_liver, thres_tumor, mode, preprocess, largest):
+    """segment_ct up to the download: the flat uint8 label volume, still on the device"""
+    shape = tuple(int(v) for v in np.shape(imgs_test)[:3])
+    coarse = coarse_liver_mask_device(model2d, imgs_test, mode=mode, preprocess=preprocess, largest=largest)
+    mask_dev, mini, maxi = liver_window_from_device_mask(coarse, shape)
+    score, score_num = sweep_scores(model_hybrid, imgs_test, 3, mini, maxi, args, mode=mode, preprocess=preprocess)
+    return _segment_liver_tumor_labels(score, score_num, shape, mask_dev, thres_liver, thres_tumor)
+
+
+def segment_ct(model2d, model_hybrid, imgs_test, args, thres_liver=0.5, thres_tumor=0.9, mode="eager", preprocess=None,
+               largest=True):
+    """the whole cascade of test.py without the `livermask/` file: the 2-D net's coarse liver mask (coarse_liver_mask_device),
+    its liver window, the z-sliding-window sweep of the hybrid net and the post-processing; returns the uint8 label volume
+    (x, y, z) that segment_volume(model_hybrid, imgs_test, <that coarse mask on the host>, args, ...) computes.  The coarse mask
+    never leaves the device: the volume goes up (once per stage), the bounding box and the labels come down.
+    `args` are the hybrid's (b = 1, input_size, input_cols); `mode` / `preprocess` apply to both stages."""
+    shape = tuple(int(v) for v in np.shape(imgs_test)[:3])
+    labels = _segment_ct_labels(model2d, model_hybrid, imgs_test, args, thres_liver, thres_tumor, mode, preprocess, largest)
+    return labels.cpu().numpy().reshape(shape)
+
+
+def evaluate_ct(model2d, model_hybrid, imgs_test, truth, args, spacing=None, thres_liver=0.5, thres_tumor=0.9, mode="eager",
+                preprocess=None, largest=True):
+    """segment_ct followed by metrics.evaluate_labels_device against the label volume `truth`, the predicted labels staying in
+    HBM in between: returns (uint8 label volume (x, y, z), {"liver": {...}, "tumor": {...}}), like evaluate_volume"""
+    from . import metrics
+    shape = tuple(int(v) for v in np.shape(imgs_test)[:3])
+    if tuple(np.shape(truth)) != shape:
+        raise ValueError("truth must have the shape of the CT volume")
+    labels = _segment_ct_labels(model2d, model_hybrid, imgs_test, args, thres_liver, thres_tumor, mode, preprocess, largest)
+    evaluation = metrics.evaluate_labels_device(labels, truth, spacing, shape=shape)
+    return labels.cpu().numpy().reshape(shape), evaluation

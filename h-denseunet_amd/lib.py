@@ -200,6 +200,9 @@ _SIGS = {
     "hdu_tile_accumulate": (c_int, [c_int, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_int, c_p, c_p, c_int,
                                     c_int, c_p, c_p]),
     "hdu_tile_finalize": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, ctypes.c_double, c_p, c_p, c_p]),
+    "hdu_slice_gather_batched": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_int, c_int, c_f, c_f, c_f, c_p, c_p]),
+    "hdu_slice_argmax_store": (c_int, [c_int, c_p, c_i64, c_i64, c_int, c_p, c_int, c_p, c_p]),
+    "hdu_slice_labels_to_raster": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
     "hdu_pp_threshold": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_p, c_p, c_p]),
     "hdu_pp_dilate": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p]),
     "hdu_pp_label": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
@@ -236,7 +239,7 @@ class HduError(RuntimeError):
     pass
 
 
-ABI_VERSION = 14       # include/hdu.h HDU_ABI_VERSION
+ABI_VERSION = 15       # include/hdu.h HDU_ABI_VERSION
 
 
 def product_library_path():

@@ -892,3 +892,37 @@ def tile_finalize(score, shape, num, channel, cx, cy, cz, thres=0.5, out_score=N
     check(_l.get().hdu_tile_finalize(_vp(score), X, Y, Z, num, channel, _vp(cx), _vp(cy), _vp(cz), float(thres),
                                      None if out_score is None else _vp(out_score), None if out_mask is None else _vp(out_mask),
                                      stream()), "hdu_tile_finalize")
+
+
+# ------------------------------------------------------------------ 2-D slice sweep step (include/hdu.h: hdu_slice_*)
+# shape = (X, Y, Z) of the volume, window = (H, W) of the 2-D model; cursor: one int32 device word, the step index.
+SLICE_MAX_BATCH = 64    # include/hdu.h HDU_SLICE_MAX_BATCH
+
+
+def slice_gather_batched(vol, shape, window, cursor, batch, dst, preprocess=None):
+    """slot i < batch of dst ([H][W][3] float32) = the planes c-1, c, c+1 (end planes replicated) of the centre plane
+    c = min(*cursor * batch + i, Z - 1) out of vol ([Z][X][Y]), cropped to the top-left H x W"""
+    X, Y, Z = shape
+    H, W = window
+    assert vol.dtype == torch.float32 and vol.is_contiguous() and vol.numel() == X * Y * Z
+    assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.numel() >= batch * H * W * 3
+    lo, hi, mean = (float(v) for v in preprocess) if preprocess is not None else (0.0, 0.0, 0.0)
+    check(_l.get().hdu_slice_gather_batched(_vp(vol), X, Y, Z, H, W, _i32p(cursor), batch, 0 if preprocess is None else 1, lo, hi,
+                                            mean, _vp(dst), stream()), "hdu_slice_gather_batched")
+
+
+def slice_argmax_store(logits, plane, Z, cursor, batch, labels):
+    """labels (uint8 [Z][plane]): the planes of the valid slots of step *cursor = argmax of the slot's logits (first maximum)"""
+    assert logits.M >= max(1, batch) * plane
+    assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.numel() == Z * plane
+    check(_l.get().hdu_slice_argmax_store(logits.dtype, logits.ptr, logits.ld, plane, Z, _i32p(cursor), batch, _vp(labels),
+                                          stream()), "hdu_slice_argmax_store")
+
+
+def slice_labels_to_raster(labels, shape, window, out):
+    """out (uint8 [X][Y][Z]) = labels (uint8 [Z][H][W]) in raster order, zero outside the H x W window"""
+    X, Y, Z = shape
+    H, W = window
+    assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.numel() == Z * H * W
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == X * Y * Z
+    check(_l.get().hdu_slice_labels_to_raster(_vp(labels), X, Y, Z, H, W, _vp(out), stream()), "hdu_slice_labels_to_raster")

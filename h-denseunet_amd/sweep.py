@@ -318,3 +318,114 @@ def tiled_plan_for(model, shape, num, preprocess=None):
         plan = TiledSweepPlan(model, shape, num, preprocess)
         model._tiled_sweep_plan = plan
     return plan
+
+
+# ------------------------------------------------------------------ 2-D slice sweep (train_2ddense.py:58-61 over every plane)
+# The 2-D DenseUNet sees the planes c-1, c, c+1 of a volume as the three channels of one input.  The step
+#
+#     hdu_slice_gather_batched -> forward over `batch` centre planes -> hdu_slice_argmax_store -> hdu_sweep_advance
+#
+# takes its step index from one device word, so it is one launch list for all ceil(Z / batch) steps; the label planes go to
+# the raster order of the post-processing once, after the last step (hdu_slice_labels_to_raster).
+class SliceSweepPlan:
+    """Resident volume, [Z][H][W] label planes, raster-order label volume and cursor of the slice sweeps of the 2-D `model` over
+    volumes of `shape`, and the step.  graph=True captures the step once and replays it per step (the step runs eagerly on the
+    emulator build); graph=False drives every step from the host with the cursor set by the host -- the same launches."""
+
+    def __init__(self, model, shape, preprocess=None):
+        if model.kind != "2d" or model.ctx.shard_world() > 1 or getattr(model, "window_batch", 1) != 1:
+            raise ValueError("the slice sweep drives the unsharded 2-D net (no window_batch)")
+        self.batch, self.H, self.W, _ = model.input_shape                  # the model window: the top-left H x W
+        self.shape = tuple(int(v) for v in shape)
+        if len(self.shape) != 3 or self.shape[0] < self.H or self.shape[1] < self.W or self.shape[2] < 1:
+            raise ValueError("volume smaller than the network window")
+        if not 1 <= self.batch <= ops.SLICE_MAX_BATCH:
+            raise ValueError("batch: 1..%d slices per forward" % ops.SLICE_MAX_BATCH)
+        self.preprocess = _check_preprocess(preprocess)
+        self.model = model
+        X, Y, Z = self.shape
+        if X * Y * Z >= 0xFFFFFFFF:
+            raise ValueError("volumes of 2^32 - 1 voxels or more are not supported")
+        dev = model.ctx.dev
+        self.plane = self.H * self.W
+        self.steps = -(-Z // self.batch)
+        self.vol = torch.zeros(Z * X * Y, dtype=torch.float32, device=dev)
+        self.planes = torch.zeros(Z * self.plane, dtype=torch.uint8, device=dev)       # argmax labels, [Z][H][W]
+        self.labels = torch.zeros(X * Y * Z, dtype=torch.uint8, device=dev)            # the same in raster order [X][Y][Z]
+        self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)                    # step index
+        self.graph = None
+        self._graph_key = None
+        self.captures = 0        # graph captures so far
+        self.replays = 0         # steps (graph replays, or eager steps) of the last sweep
+
+    def key(self):
+        return (self.shape, self.preprocess)
+
+    def _step(self):
+        m = self.model
+        ops.slice_gather_batched(self.vol, self.shape, (self.H, self.W), self.cursor, self.batch, m.x_stage, self.preprocess)
+        m.ctx.run_forward()
+        ops.slice_argmax_store(m.logits.act, self.plane, self.shape[2], self.cursor, self.batch, self.planes)
+        ops.sweep_advance(self.cursor, self.steps)
+
+    def _capture(self):
+        """one eager warm-up step on a side stream, then the step into a linear graph (as SweepPlan._capture)"""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self._step()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        from .keras_api import _graph_capture
+        with _graph_capture(g):
+            self._step()
+        self.graph = g
+        self._graph_key = self.model._predict_state()
+        self.captures += 1
+
+    def prepare(self):
+        """weights and inference-mode BN coefficients of this sweep, once (learning_phase must be 0)"""
+        ctx = self.model.ctx
+        ctx.prep_weights()
+        ctx.prefold()
+
+    def sweep(self, imgs_test, graph=True):
+        """-> the uint8 label volume {0, 1, 2} as a flat device tensor in raster order [X][Y][Z], zero outside the model window:
+        the plan's own buffer, valid until the next sweep of this plan"""
+        if tuple(int(v) for v in np.shape(imgs_test)[:3]) != self.shape:
+            raise ValueError("this plan sweeps volumes of shape %s" % (self.shape,))
+        vol = np.ascontiguousarray(np.asarray(imgs_test, np.float32).reshape(self.shape).transpose(2, 0, 1))
+        self.vol.copy_(torch.from_numpy(vol).reshape(-1))
+        ctx = self.model.ctx
+        use_graph = graph and not _l.is_emulator()
+        ctx.learning_phase = 0
+        try:
+            self.prepare()
+            if use_graph and (self.graph is None or self._graph_key != self.model._predict_state()):
+                self._capture()              # (its warm-up step dirties the label planes and the cursor: every valid plane is
+            self.cursor.zero_()              #  written again below, and the cursor is reset here)
+            self.replays = 0
+            for step in range(self.steps):
+                if use_graph:
+                    self.graph.replay()
+                else:
+                    if not graph:
+                        self.cursor.fill_(step)      # host-driven: the advance launch below computes the same word
+                    self._step()
+                self.replays += 1
+        finally:
+            ctx.end_prefold()
+            ctx.learning_phase = 1
+        ops.slice_labels_to_raster(self.planes, self.shape, (self.H, self.W), self.labels)
+        return self.labels
+
+
+def slice_plan_for(model, shape, preprocess=None):
+    """the 2-D model's slice plan for this volume shape (one plan is kept per model, keyed by shape and preprocessing)"""
+    plan = getattr(model, "_slice_sweep_plan", None)
+    key = (tuple(int(v) for v in shape), _check_preprocess(preprocess))
+    if plan is None or plan.key() != key:
+        plan = SliceSweepPlan(model, shape, preprocess)
+        model._slice_sweep_plan = plan
+    return plan

@@ -48,7 +48,7 @@ const char* hdu_backend(void);
  * 10 = hdu_bn_bwd_fused_pw, hdu_colsum_fold_batched, column-sum table arguments of hdu_bn_bwd_fused / hdu_bn_bwd_apply_sums,
  * 12 = y_ds / ldy_ds / ds_accumulate / ds_only (the up-sampling gradient in the halo-wide data-gradient epilogue),
  * 14 = hdu_metric_* (device-resident segmentation metrics). */
-#define HDU_ABI_VERSION 14
+#define HDU_ABI_VERSION 15
 int hdu_abi_version(void);
 size_t hdu_sizeof_conv_desc(void);
 /* Launch profiler (measurement only; replaces nothing in the reference -- Keras has `verbose`, the reference was profiled with
@@ -628,6 +628,37 @@ int hdu_tile_accumulate(int dtype, const void* logits, int64_t ldl, int X, int Y
                         float* score, void* stream);
 int hdu_tile_finalize(const float* score, int X, int Y, int Z, int num, int channel, const float* cx, const float* cy,
                       const float* cz, double thres, float* out_score, uint8_t* out_mask, void* stream);
+
+/* 2-D slice sweep (train_2ddense.py:58-61 samples the planes c-1, c, c+1 of a volume as the three channels of one 2-D input;
+ * h-denseunet_amd/sweep.py SliceSweepPlan runs the 2-D DenseUNet over EVERY plane of a resident volume and keeps the argmax).
+ * Layouts: resident volume float32 [Z][X][Y] (depth-major), model input float32 [batch][H][W][3] (Model.x_stage), logits
+ * [batch*H*W][ldl] in the compute dtype (3 classes in the first channels), label planes uint8 [Z][H*W].  The model window is
+ * the top-left H x W of each plane (H <= X, W <= Y: the crop rule of the z-sweep).  The step index is ONE int32 device word
+ * (cursor), so one launch list serves every step; nsteps = ceil(Z / batch) and the kernels clamp *cursor to [0, nsteps-1].
+ * Slot i of step s has the centre plane c_i = min(s*batch + i, Z-1) and is VALID iff s*batch + i < Z.
+ * hdu_slice_gather_batched: dst[i][h][w][k] = f(vol[clamp(c_i + k - 1, 0, Z-1)][h][w]), k = 0..2.  The END PLANES ARE
+ *   REPLICATED: plane -1 reads plane 0 and plane Z reads plane Z-1 (Z = 1: all three channels are the one plane).  The
+ *   reference never samples there (train_2ddense.py:59 draws c inside the liver box, away from the ends), so this rule is this
+ *   library's own.  Slots that are not valid repeat the last plane (c_i = Z-1), so the forward always runs on finite data.
+ *   f: preprocess == 0 moves the bits unchanged; otherwise min(max(v, lo), hi) - mean in float32, the very expression of
+ *   hdu_sweep_gather.  16-byte stores with a scalar head and tail per slot (a slot base is 4-byte aligned only); the loads of
+ *   neighbouring lanes run along y.
+ * hdu_slice_argmax_store: plane = H*W; for every valid slot, labels[s*batch + i][p] = the index of the largest of the three
+ *   logits of row i*plane + p, compared with a strict `>` in slot order 0, 1, 2: the FIRST maximum wins (np.argmax), -0.0 and
+ *   +0.0 tie.  No softmax and no threshold: softmax is monotonic, and a comparison of logits is exact in both dtypes.  Slots that
+ *   are not valid write nothing; nothing outside labels[0 .. Z*plane) is written.  Logits are taken as finite.
+ * hdu_slice_labels_to_raster: out uint8 [X][Y][Z], the raster order of the hdu_pp_* / hdu_metric_* kernels:
+ *   out[x][y][z] = labels[z][x][y] for x < H and y < W, 0 elsewhere; EVERY byte of out is written.  For one x a 64 (z) x 64 (y)
+ *   byte tile goes through LDS: global reads run along y, global writes along z.
+ * 1 <= batch <= HDU_SLICE_MAX_BATCH, Z >= 1, 1 <= H <= X, 1 <= W <= Y, ldl >= 3, volumes below 2^32 - 1 voxels, non-NULL
+ * pointers (float32 / int32 buffers 4-byte aligned), a known dtype; a bad argument returns HDU_ERR_ARG and launches nothing.
+ * hdu_sweep_advance serves unchanged, with nsteps as its bound. */
+#define HDU_SLICE_MAX_BATCH 64
+int hdu_slice_gather_batched(const float* vol, int X, int Y, int Z, int H, int W, const int32_t* cursor, int batch,
+                             int preprocess, float lo, float hi, float mean, float* dst, void* stream);
+int hdu_slice_argmax_store(int dtype, const void* logits, int64_t ldl, int64_t plane, int Z, const int32_t* cursor, int batch,
+                           uint8_t* labels, void* stream);
+int hdu_slice_labels_to_raster(const uint8_t* labels, int X, int Y, int Z, int H, int W, uint8_t* out, void* stream);
 
 /* ------------------------------------------------------------------ per-step re-initialisation
  * The accumulators a training step adds into (epilogue statistics, fused BN-backward slot rows, the flat gradient buffer the
